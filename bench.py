@@ -28,6 +28,12 @@ scaling curve come from the same code (same-box A/B at N = 1: profiles/engine_ab
 Python one for ResNet-50 and larger batches (1-2% faster there). A C++ run that fails on any rank
 (the ranks agree over a CPU-only gloo group of this launcher process; no GPU work in it) falls back
 to the Python engine on every rank.
+
+A plain run does what the headline figure needs and nothing else: set-up, --warmup steps, --steps
+timed steps, the result line (`ms_per_step`: milliseconds per timed step). --dump-outputs DIR
+also writes what the last timed step left with its caller as DIR/loss.npy and DIR/params.npy
+(either engine; the seeds are fixed, so the same arguments give the same inputs in every run).
+--full is where measurements beyond the headline figure go; the benchmark has none today.
 """
 import argparse
 import json
@@ -70,6 +76,15 @@ def native_main(a):
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     if (a.device, a.dtype) not in (("cuda", "bf16"), ("cpu", "fp32")):
         raise SystemExit("--engine native: bf16 on GPUs (or the fp32 CPU backend)")
+    if a.device == "cuda":
+        # GPU runs: the launcher maps the package's HIP kernel library as well (built from the kernel
+        # sources that the trainer's libdcnn.so links), so the benchmark's own process, not only its
+        # child, runs with the project's native code loaded. No GPU call is made here. A tree without
+        # the library counts as a failed C++ engine on every rank, like any other missing piece.
+        try:
+            import dcnn_amd._kernels  # noqa: F401
+        except ImportError as e:
+            raise NativeFailed(f"the HIP kernel library does not load ({e})")
     model = a.model
     if os.environ.get("DCNN_BENCH_FAULT_RANK") == str(rank):  # (tests: this rank's child fails)
         model = "no_such_model"
@@ -77,6 +92,8 @@ def native_main(a):
            "GPU" if a.device == "cuda" else "CPU", "--model", model,
            "--batch", str(a.batch), "--steps", str(a.steps), "--warmup", str(a.warmup), "--loss", "softmax_ce",
            "--bench"] + (["--dp"] if world > 1 else [])
+    if a.dump_outputs:  # (rank 0's child writes DIR/loss.npy + DIR/params.npy after its timed steps)
+        cmd += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     env.setdefault("MASTER_PORT", "29533")
@@ -114,7 +131,8 @@ def native_main(a):
     C, H, W = INPUT_SHAPES[a.model]
     print(json.dumps({
         "metric": METRIC if a.model == "resnet18_tiny_imagenet" else f"images/sec (whole node) {a.model} training",
-        "value": round(d["value"], 2), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "value": round(d["value"], 2), "unit": "images/sec", "n_gpus": world, "steps": a.steps,
+        "warmup": d.get("warmup", a.warmup),  # (the trainer runs at least one warm-up step and says how many ran)
         "ms_per_step": round(d["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": a.dtype, "data": d.get("data", f"synthetic {H}x{W}x{C}"),
         "config": {"model": a.model, "global_batch": a.batch * world, "per_gpu_batch": a.batch, "seq_len": None,
@@ -124,6 +142,18 @@ def native_main(a):
                    "hipgraph": d.get("hipgraph"), "final_loss": round(d.get("loss", float("nan")), 4),
                    "f32_mode": None, "engine": "native (C++ host API)"},
     }), flush=True)
+
+
+def dump_outputs(path, model, loss_val):
+    """--dump-outputs on the Python engine, the files the C++ trainer writes: what the last timed
+    step left with its caller. loss.npy (float64, 1 value) and params.npy (float32: every parameter
+    flattened, in model order; above 12M parameters every stride-th element, below 48 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([loss_val], dtype=np.float64))
+    flat = torch.cat([p.detach().reshape(-1).float().cpu() for p in model.parameters()])
+    stride = (flat.numel() + 12000000 - 1) // 12000000
+    np.save(os.path.join(path, "params.npy"), flat[::stride].contiguous().numpy())
 
 
 def auto_native(a):
@@ -172,7 +202,18 @@ def main():
                          "(v_mfma_f32_16x16x4_f32) everywhere; concat = 3xbf16 split precision on the "
                          "halo convs ([hi|lo|hi] channels, ~2^-16 relative per product) + exact elsewhere; "
                          "split = 3xbf16 on the gathered GEMMs too")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left with its caller (rank 0): "
+                         "DIR/loss.npy (float64) and DIR/params.npy (float32, the trained parameters). Seeds are "
+                         "fixed, so the same arguments give the same inputs in every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the benchmark measures beyond its headline figure. A plain run already "
+                         "does nothing but set up, warm up, time --steps steps and print the result line (the "
+                         "per-layer times stay behind --profile, other models / precisions / engines behind their "
+                         "own options), so today --full adds nothing")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.engine == "native":
         try:
             return native_main(a)
@@ -268,6 +309,8 @@ def main():
     ms = el / a.steps * 1e3
     imgs = a.batch * world * a.steps / el
     timed_with_graph = bool(step.use_graph)  # what the timed loop ran (--profile switches it off below)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, loss_val)
     if rank == 0:
         print(json.dumps({
             "metric": METRIC if a.model == "resnet18_tiny_imagenet" else f"images/sec (whole node) {a.model} training",

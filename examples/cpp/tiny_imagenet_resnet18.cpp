@@ -4,7 +4,8 @@
 //   dcnn_amd/bin/tiny_imagenet_resnet18 [--device CPU|GPU] [--model resnet18_tiny_imagenet]
 //        [--data data/tiny-imagenet-200] [--epochs E] [--steps S] [--batch B] [--lr 1e-3]
 //        [--loss logsoftmax_ce] [--scheduler cosine_annealing_lr] [--max-per-class K]
-//        [--save model_snapshots/resnet18] [--bench [--eager] [--warmup W]] [--dp] [--device-data]
+//        [--save model_snapshots/resnet18] [--bench [--eager] [--warmup W] [--dump-outputs DIR]] [--dp]
+//        [--device-data]
 //
 // Without --data it trains on a learnable synthetic 3x64x64 200-class set. --device-data (GPU, with
 // --data): the GPU data path (DeviceImageDataset): the decoded set lives in HBM as uint8 and every
@@ -12,8 +13,11 @@
 // the training flow — with --bench that launch is inside every timed step. --bench times
 // --steps training steps after --warmup (3) warm-up steps on two device-resident synthetic batches and
 // prints one JSON line (images/sec); on the GPU the step is captured into a hipGraph
-// (dcnn::TrainGraph) and replayed, --eager launches every kernel from the host instead. The saved
-// model (path.json + path.bin + path.bnstats) loads in Python with Sequential.from_file.
+// (dcnn::TrainGraph) and replayed, --eager launches every kernel from the host instead.
+// --dump-outputs DIR (--bench): after the timed steps, the last step's loss and the trained
+// parameters as DIR/loss.npy and DIR/params.npy (the seeds are fixed: the same arguments give the
+// same inputs in every run), written before the JSON line. The saved model (path.json + path.bin +
+// path.bnstats) loads in Python with Sequential.from_file.
 // --dp (--bench): data parallel, one process per GPU under the torch.distributed launcher's
 // variables (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT; dcnn/dist.hpp): rank 0's
 // weights are broadcast, each rank trains --batch samples per step, the bucketed gradient mean runs
@@ -27,9 +31,11 @@
 #include <functional>
 #include <cstdio>
 #include <cstdlib>
+#include <filesystem>
 #include <iostream>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "dcnn/dist.hpp"
 #include "dcnn/nn.hpp"
@@ -42,11 +48,46 @@ std::string env_or(const char* k, const std::string& d) {
   const char* v = std::getenv(k);
   return v && *v ? v : d;
 }
+
+// one 1-D little-endian array as a NumPy .npy file (format 1.0); descr "<f4" or "<f8"
+void write_npy(const std::string& path, const char* descr, const void* data, size_t n, size_t elem) {
+  std::string h = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (";
+  h += std::to_string(n) + ",), }";
+  h.append(63 - (10 + h.size()) % 64, ' ');  // magic + version + length + header + '\n': a multiple of 64
+  h.push_back('\n');
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("--dump-outputs: cannot write " + path);
+  const unsigned char pre[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(h.size() & 255),
+                                 (unsigned char)(h.size() >> 8)};
+  const bool ok = std::fwrite(pre, 1, 10, f) == 10 && std::fwrite(h.data(), 1, h.size(), f) == h.size() &&
+                  std::fwrite(data, elem, n, f) == n;
+  if (std::fclose(f) != 0 || !ok) throw std::runtime_error("--dump-outputs: short write to " + path);
+}
+
+// what the last timed step left with its caller: loss.npy (float64, 1 value) and params.npy
+// (float32: every parameter in checkpoint order, logical layout, flattened; models above 12M
+// parameters: every stride-th element of that vector, so the file stays below 48 MB)
+void dump_outputs(const std::string& dir, Sequential& model, double loss) {
+  std::filesystem::create_directories(dir);
+  write_npy(dir + "/loss.npy", "<f8", &loss, 1, sizeof loss);
+  std::vector<float> all;
+  for (Param* p : model.parameters()) {
+    const std::vector<float> v = p->value.view(p->shape, p->layout).to_host_f32();
+    all.insert(all.end(), v.begin(), v.end());
+  }
+  const size_t stride = (all.size() + 12000000 - 1) / 12000000;
+  if (stride > 1) {
+    size_t m = 0;
+    for (size_t i = 0; i < all.size(); i += stride) all[m++] = all[i];
+    all.resize(m);
+  }
+  write_npy(dir + "/params.npy", "<f4", all.data(), all.size(), sizeof(float));
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   std::string device = env_or("DEVICE_TYPE", "CPU"), data, save, model_name = "resnet18_tiny_imagenet";
-  std::string loss_name = "logsoftmax_ce", sched_name;
+  std::string loss_name = "logsoftmax_ce", sched_name, dump_dir;
   int epochs = std::atoi(env_or("EPOCHS", "1").c_str()), steps = -1, max_per_class = 0, warmup = 3;
   int batch = std::atoi(env_or("BATCH_SIZE", "64").c_str());
   float lr = std::atof(env_or("LR_INITIAL", "0.001").c_str());
@@ -71,6 +112,7 @@ int main(int argc, char** argv) {
     else if (k == "--max-per-class") max_per_class = std::atoi(v.c_str());
     else if (k == "--save") save = v;
     else if (k == "--warmup") warmup = std::atoi(v.c_str());
+    else if (k == "--dump-outputs") dump_dir = v;
   }
   try {
     Sequential model = create_model(model_name);
@@ -173,7 +215,8 @@ int main(int argc, char** argv) {
         opt.step(model.parameters());
         return r.loss;
       };
-      for (int i = 0; i < std::max(1, warmup); ++i) one();
+      const int warm = std::max(1, warmup);  // (at least one: the JSON line reports the count that ran)
+      for (int i = 0; i < warm; ++i) one();
       // the timed region is bracketed by a device synchronisation + a barrier over the ranks on
       // both sides; the slowest rank's time is reported
       auto fence = [&] {
@@ -189,11 +232,12 @@ int main(int argc, char** argv) {
       if (graph) last = tg.last_loss();
       const int world = dp ? dp->world() : 1;
       if (dp) s = dp->max(s);  // the slowest rank
+      if (!dump_dir.empty() && (!dp || dp->rank() == 0)) dump_outputs(dump_dir, model, last);
       if (!dp || dp->rank() == 0)
         std::printf("{\"metric\": \"images/sec %s training (C++ host API)\", \"value\": %.1f, \"ms_per_step\": %.3f, "
-                    "\"batch\": %d, \"steps\": %d, \"device\": \"%s\", \"hipgraph\": %s, \"loss\": %.6f, "
-                    "\"world\": %d, \"data_parallel\": %s%s%s, \"dp_buckets\": %d, \"data\": \"%s, random init\"}\n",
-                    model_name.c_str(), (double)batch * world * timed / s, 1e3 * s / timed, batch, timed,
+                    "\"batch\": %d, \"steps\": %d, \"warmup\": %d, \"device\": \"%s\", \"hipgraph\": %s, "
+                    "\"loss\": %.6f, \"world\": %d, \"data_parallel\": %s%s%s, \"dp_buckets\": %d, \"data\": \"%s, random init\"}\n",
+                    model_name.c_str(), (double)batch * world * timed / s, 1e3 * s / timed, batch, timed, warm,
                     dev.str().c_str(), graph ? "true" : "false", last, world, dp ? "\"" : "", dp ? dp->plane() : "null",
                     dp ? "\"" : "", dp ? dp->buckets_last_step() : 0,
                     data.empty() ? "synthetic: 2 device-resident batches per rank of a learnable class-template set "

@@ -468,3 +468,29 @@ def test_bench_default_engine_contract_line(bins, tmp_path):
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["dtype"] == "bf16"
     assert d["config"]["engine"] == "native (C++ host API)" and d["config"]["global_batch"] == 64
     assert abs(d["value"] - 64 * 1000.0 / d["ms_per_step"]) < 0.02 * d["value"]
+
+
+@pytest.mark.gpu
+def test_bench_default_engine_dump_outputs(bins, tmp_path):
+    """`python bench.py --dump-outputs DIR` on one GPU: the C++ engine's last timed step as
+    DIR/loss.npy (float64, the line's final_loss) and DIR/params.npy (float32, all of ResNet-18's
+    parameters, finite). They are the parameters the last timed step left: a run of one step fewer
+    leaves other values (Adam moves every parameter with a non-zero gradient by about the learning
+    rate per step)."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = {}
+    for steps in (4, 3):
+        out = tmp_path / f"out{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "64", "--steps",
+                            str(steps), "--warmup", "2", "--dump-outputs", str(out)],
+                           cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["warmup"] == 2 and d["config"]["engine"] == "native (C++ host API)"
+        assert sorted(os.listdir(out)) == ["loss.npy", "params.npy"]
+        loss, params = np.load(out / "loss.npy"), np.load(out / "params.npy")
+        assert loss.dtype == np.float64 and loss.shape == (1,) and abs(loss[0] - d["config"]["final_loss"]) < 1e-4
+        assert params.dtype == np.float32 and params.shape == (11258088,) and np.isfinite(params).all()
+        outs[steps] = (loss, params)
+    assert outs[3][0][0] != outs[4][0][0] and np.mean(outs[3][1] != outs[4][1]) > 0.5
