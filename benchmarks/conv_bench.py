@@ -3,6 +3,11 @@
 ResNet-18-tiny layer shapes. Reports device time per call and achieved TFLOP/s.
 
   python benchmarks/conv_bench.py --batch 256 [--only fwd|dgrad|wgrad] [--iters 20]
+
+--depthwise: the depthwise-conv streaming kernels (dwconv.hip) at the MobileNetV1-Tiny-ImageNet
+shapes instead — per pass the device time, the compulsory GB/s, a plain device copy moving the
+same number of bytes, PyTorch's F.conv2d(groups=C) passes (bf16 channels_last) and, with --step,
+the captured training step of mobilenet_v1_tiny_imagenet on the Python engine.
 """
 import argparse
 import os
@@ -50,6 +55,129 @@ SHAPES_R50 = [
 ]
 
 
+# every distinct depthwise (C, H, W, stride) of mobilenet_v1_tiny_imagenet (3x3, pad 1)
+SHAPES_DW = [(32, 64, 64, 1), (64, 64, 64, 2), (128, 32, 32, 1), (128, 32, 32, 2), (256, 16, 16, 1), (256, 16, 16, 2),
+             (512, 8, 8, 1), (512, 8, 8, 2), (1024, 4, 4, 1)]
+
+
+def _time_graph(fn, iters, reps):
+    """Median / min / max device microseconds per call over `reps` replays of a graph of `iters`
+    calls (no host launch overhead); eager launches if the calls cannot be captured."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    try:
+        g = torch.cuda.CUDAGraph()
+        s_ = torch.cuda.Stream()
+        s_.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s_):
+            with torch.cuda.graph(g, stream=s_):
+                for _ in range(iters):
+                    fn()
+        torch.cuda.current_stream().wait_stream(s_)
+        run, mode = g.replay, "graph"
+    except Exception:  # noqa: BLE001 (a library call that allocates or synchronises inside the capture)
+        torch.cuda.synchronize()
+
+        def run():
+            for _ in range(iters):
+                fn()
+        mode = "eager"
+    run()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(reps):
+        e0.record()
+        run()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) * 1000 / iters)
+    us.sort()
+    return us[len(us) // 2], us[0], us[-1], mode
+
+
+def depthwise_main(a):
+    import json
+    import torch.nn.functional as F
+    from dcnn_amd.ops import hip
+    CL = torch.channels_last
+    N = a.batch
+    rows = []
+    print(f"{'shape':<18}{'op':<7}{'us':>9}{'min':>9}{'max':>9}{'GB/s':>8}{'copy us':>9}{'% copy':>8}{'torch us':>10}"
+          f"{'torch/ours':>11}")
+    for (C, H, W, s) in SHAPES_DW:
+        OH, OW = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+        x = torch.randn(N, C, H, W, device="cuda").bfloat16().contiguous(memory_format=CL)
+        w = (torch.randn(C, 1, 3, 3, device="cuda") / 3).bfloat16()
+        dy = torch.randn(N, C, OH, OW, device="cuda").bfloat16().contiguous(memory_format=CL)
+        gw = torch.zeros(C, 1, 3, 3, device="cuda")
+        xb, yb = 2.0 * N * H * W * C, 2.0 * N * OH * OW * C
+        # compulsory bytes: each activation read or written once (weights and slabs are < 1 %)
+        hbm = {"fwd": xb + yb, "dgrad": xb + yb, "wgrad": xb + yb}
+        ops = {"fwd": lambda: hip.dwconv2d_fwd(x, w, None, (s, s), (1, 1)),
+               "dgrad": lambda: hip.dwconv2d_dgrad(dy, w, tuple(x.shape), (s, s), (1, 1)),
+               "wgrad": lambda: hip.dwconv2d_wgrad(dy, x, tuple(w.shape), (s, s), (1, 1), gw, None)}
+        aten = torch.ops.aten.convolution_backward
+        bwd = lambda mask: aten(dy, x, w, None, [s, s], [1, 1], [1, 1], False, [0, 0], C, mask)  # noqa: E731
+        tops = {"fwd": lambda: F.conv2d(x, w, None, s, 1, groups=C),
+                "dgrad": lambda: bwd([True, False, False]), "wgrad": lambda: bwd([False, True, False])}
+        for op, fn in ops.items():
+            if a.only and op != a.only:
+                continue
+            us, lo, hi, _ = _time_graph(fn, a.iters, a.reps)
+            # a flat copy moving the same bytes (half of them read, half written)
+            n = int(hbm[op] / 2) // 2
+            src, dst = torch.empty(n, device="cuda", dtype=torch.bfloat16), torch.empty(n, device="cuda", dtype=torch.bfloat16)
+            cus, _, _, _ = _time_graph(lambda: dst.copy_(src), a.iters, a.reps)
+            del src, dst
+            tus, tmode = float("nan"), "-"
+            if a.torch_ref:
+                tus, _, _, tmode = _time_graph(tops[op], a.iters, a.reps)
+            r = dict(C=C, H=H, W=W, stride=s, op=op, us=us, us_min=lo, us_max=hi, gbs=hbm[op] / us / 1e3, copy_us=cus,
+                     pct_copy=100.0 * cus / us, torch_us=tus, torch_mode=tmode, torch_over_ours=tus / us)
+            rows.append(r)
+            print(f"{f'c{C} {H}x{W} s{s}':<18}{op:<7}{us:9.1f}{lo:9.1f}{hi:9.1f}{r['gbs']:8.0f}{cus:9.1f}{r['pct_copy']:8.1f}"
+                  f"{tus:10.1f}{tus / us:11.2f}", flush=True)
+            if a.json:
+                with open(a.json, "w") as f:
+                    json.dump(dict(batch=N, iters=a.iters, reps=a.reps, rows=rows), f, indent=1)
+    step = None
+    if a.step:
+        from dcnn_amd.models import create_model
+        from dcnn_amd.nn import Adam, LossFactory
+        from dcnn_amd.runtime.step import TrainStep
+        m = create_model("mobilenet_v1_tiny_imagenet")
+        m.set_seed(1)
+        m.set_device("GPU:0")
+        m.initialize()
+        m.set_first_layer_input_grad(False)
+        opt = Adam(1e-3)
+        opt.attach(m)
+        st = TrainStep(m, LossFactory.create("softmax_crossentropy"), opt, use_graph=True)
+        xs = torch.randn(N, 3, 64, 64, device="cuda")
+        ys = torch.randint(0, 200, (N,), device="cuda")
+        for _ in range(6):
+            st(xs, ys)
+        torch.cuda.synchronize()
+        ms = []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(a.reps):
+            e0.record()
+            for _ in range(20):
+                st(xs, ys)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / 20)
+        ms.sort()
+        step = dict(model="mobilenet_v1_tiny_imagenet", batch=N, graph=st.graphs is not None, ms=ms[len(ms) // 2],
+                    ms_min=ms[0], ms_max=ms[-1], img_s=N * 1000.0 / ms[len(ms) // 2], loss=float(st.last_loss.item()))
+        print("training step:", step, flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(batch=N, iters=a.iters, reps=a.reps, rows=rows, step=step), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -69,7 +197,14 @@ def main():
                     help="dgrad with the production epilogue: the consuming BatchNorm's ReLU mask (y) and "
                          "backward statistics (x, mean, istd) fused in (BnbRequest)")
     ap.add_argument("--no-group", action="store_true", help="strided dgrad phases as separate launches")
+    ap.add_argument("--depthwise", action="store_true", help="depthwise kernels at the MobileNetV1-tiny shapes")
+    ap.add_argument("--reps", type=int, default=5, help="--depthwise: timed replays per figure (median, min, max)")
+    ap.add_argument("--torch-ref", type=int, default=1, help="--depthwise: also time PyTorch's grouped conv passes")
+    ap.add_argument("--step", action="store_true", help="--depthwise: also time the captured MobileNetV1 training step")
+    ap.add_argument("--json", default="", help="--depthwise: write the figures to this file as they come")
     a = ap.parse_args()
+    if a.depthwise:
+        return depthwise_main(a)
     from dcnn_amd.ops import hip, fusion
     if a.split_target is not None:
         hip.kernels().hconv_set_split_target(a.split_target)

@@ -99,6 +99,30 @@ int dcnn_c_conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const
   });
 }
 
+// depthwise conv (shape[4] Co == shape[1] C): y = dwconv(x, w) + bias, w bf16 [C][KH][KW]
+int dcnn_c_dwconv_fwd(const void* x, const void* w, const float* bias, void* y, const int* shape) {
+  return guarded([&] { gpu_ops::dwconv_fwd(x, w, bias, y, shape_of(shape)); });
+}
+
+// dx = dwconv^T(dy, w) (+ residual)
+int dcnn_c_dwconv_dgrad(const void* dy, const void* w, void* dx, const int* shape, const void* residual) {
+  return guarded([&] { gpu_ops::dwconv_dgrad(dy, w, dx, shape_of(shape), residual); });
+}
+
+// gw / gb (+=) the weight / bias gradient; deferred: inside a backward's batched split-K reduce
+int dcnn_c_dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const int* shape, int deferred) {
+  return guarded([&] {
+    if (deferred) gpu_ops::begin_deferred_reduce();
+    try {
+      gpu_ops::dwconv_wgrad(dy, x, gw, gb, shape_of(shape));
+    } catch (...) {
+      if (deferred) gpu_ops::end_deferred_reduce();
+      throw;
+    }
+    if (deferred) gpu_ops::end_deferred_reduce();
+  });
+}
+
 int dcnn_c_stem_fwd(const float* x, const void* w, const float* bias, void* y, const int* shape, int want_stats,
                     const float** slab, int* rows) {
   return guarded([&] {

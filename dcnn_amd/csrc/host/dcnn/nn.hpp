@@ -159,6 +159,27 @@ class Conv2D : public Layer {
   const void* dgrad_operand(bool& transposed) const;
 };
 
+// Depthwise convolution (groups = C, channel multiplier 1): weights (C, 1, KH, KW). Not a Conv2D:
+// the fusion planner sees FK_OTHER (no statistics epilogue, no backward-BatchNorm fusion, no
+// transposed operand); the BatchNorm around it runs its own statistics passes.
+class DepthwiseConv2D : public Layer {
+ public:
+  DepthwiseConv2D(int channels, int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0, bool bias = true,
+                  std::string name = "depthwise_conv2d");
+  std::string type() const override { return "depthwise_conv2d"; }
+  json::Value parameters_config() const override;
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override;
+  Tensor backward(const Tensor& dy) override;
+  double flops(const std::vector<int64_t>& in) const override;
+
+ private:
+  ConvShape shape_for(const std::vector<int64_t>& in) const;
+  int c_, kh_, kw_, sh_, sw_, ph_, pw_;
+  bool bias_;
+};
+
 class Dense : public Layer {
  public:
   Dense(int in_features, int out_features, bool bias = true, std::string name = "dense");
@@ -448,6 +469,9 @@ class SequentialBuilder {
   SequentialBuilder& input(const std::vector<int64_t>& chw);
   SequentialBuilder& conv2d(int out_ch, int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0,
                             bool bias = true, const std::string& name = "");
+  // channels from the running shape
+  SequentialBuilder& depthwise_conv2d(int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0, bool bias = true,
+                                      const std::string& name = "");
   SequentialBuilder& batchnorm(float eps = 1e-5f, float momentum = 0.1f, bool affine = true,
                                const std::string& name = "");
   SequentialBuilder& activation(const std::string& kind = "relu", const std::string& name = "");

@@ -18,6 +18,9 @@ enum ActKind { ACT_RELU = 0, ACT_LEAKY_RELU = 1, ACT_ELU = 2, ACT_SIGMOID = 3, A
 namespace cpu_ops {
 void conv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s);
 void conv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s);
+// depthwise conv (groups = C, channel multiplier 1; s.Co == s.C): w [C][KH][KW]; dx may be null
+void dwconv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s);
+void dwconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s);
 void dense_fwd(const float* x, const float* w, const float* b, float* y, long N, long In, long Out);
 void dense_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, long N, long In,
                long Out);
@@ -100,6 +103,12 @@ void weight_transpose(const void* w, void* wt, int Co, int T, int C);
 void multi_weight_transpose(const int64_t* table, int n, long max_tiles);
 // gw fp32 [Co][KH][KW][C] and gb fp32 [Co] accumulate (+=); gb may be null
 void conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s);
+// depthwise conv (dwconv.hip; s.Co == s.C): bf16 NHWC activations, w bf16 [C][KH][KW], bias fp32
+// or null; a shape the kernels do not take throws. dgrad: dx = conv^T(dy, w) (+ residual);
+// wgrad: gw fp32 [C][KH][KW] and gb fp32 [C] accumulate (+=) through wgrad_slab / wgrad_reduce
+void dwconv_fwd(const void* x, const void* w, const float* bias, void* y, const ConvShape& s);
+void dwconv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, const void* residual = nullptr);
+void dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s);
 // the network's first conv straight from the fp32 NCHW input (RGB stem kernel: <= 4 input
 // channels, 3x3 stride-1 'same', 16-multiple outputs up to 64); y bf16 NHWC
 bool stem_ok(const ConvShape& s);

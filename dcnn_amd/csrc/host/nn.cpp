@@ -246,6 +246,97 @@ Tensor Conv2D::backward_residual(const Tensor& dy, const Tensor& residual) {
   return dx;
 }
 
+// ------------------------------------------------------------------ DepthwiseConv2D
+DepthwiseConv2D::DepthwiseConv2D(int channels, int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
+                                 std::string name)
+    : Layer(std::move(name)), c_(channels), kh_(kh), kw_(kw), sh_(sh), sw_(sw), ph_(ph), pw_(pw), bias_(bias) {}
+
+json::Value DepthwiseConv2D::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["channels"] = c_;
+  p["kernel_h"] = kh_;
+  p["kernel_w"] = kw_;
+  p["stride_h"] = sh_;
+  p["stride_w"] = sw_;
+  p["pad_h"] = ph_;
+  p["pad_w"] = pw_;
+  p["use_bias"] = bias_;
+  return p;
+}
+
+ConvShape DepthwiseConv2D::shape_for(const std::vector<int64_t>& in) const {
+  ConvShape s{};
+  s.N = (int)in[0];
+  s.C = (int)in[1];
+  s.H = (int)in[2];
+  s.W = (int)in[3];
+  s.Co = c_;
+  s.KH = kh_;
+  s.KW = kw_;
+  s.SH = sh_;
+  s.SW = sw_;
+  s.PH = ph_;
+  s.PW = pw_;
+  s.OH = (s.H + 2 * ph_ - kh_) / sh_ + 1;
+  s.OW = (s.W + 2 * pw_ - kw_) / sw_ + 1;
+  if (s.C != c_) throw std::runtime_error(name_ + ": input has " + std::to_string(s.C) + " channels, expected " +
+                                          std::to_string(c_));
+  return s;
+}
+
+std::vector<int64_t> DepthwiseConv2D::output_shape(const std::vector<int64_t>& in) const {
+  const ConvShape s = shape_for(in);
+  return {in[0], c_, s.OH, s.OW};
+}
+
+void DepthwiseConv2D::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+  (void)in;
+  dev_ = dev;
+  params_.clear();
+  const float bound = 1.f / std::sqrt((float)(kh_ * kw_));  // Conv2D's rule, one input channel per group
+  // (C, 1, KH, KW): NCHW and NHWC are the same bytes [C][KH][KW]
+  add_param("weights", {c_, 1, kh_, kw_}, Layout::NCHW, uniform_init((size_t)c_ * kh_ * kw_, bound, seed));
+  if (bias_) add_param("bias", {c_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)c_, bound, seed + 1));
+}
+
+double DepthwiseConv2D::flops(const std::vector<int64_t>& in) const {
+  const ConvShape s = shape_for(in);
+  const double out = (double)s.N * s.OH * s.OW;
+  return 6.0 * c_ * kh_ * kw_ * out + (bias_ ? 2.0 * c_ * out : 0.0);  // forward 2, backward 4 per MAC
+}
+
+Tensor DepthwiseConv2D::forward(const Tensor& x, bool training) {
+  (void)training;
+  check_act(x, dev_, "depthwise_conv2d");
+  const ConvShape s = shape_for(x.shape());
+  Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
+  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
+  if (dev_.is_gpu())
+    gpu_ops::dwconv_fwd(x.data(), params_[0].shadow.data(), b, y.data(), s);
+  else
+    cpu_ops::dwconv_fwd(x.ptr<float>(), params_[0].value.ptr<float>(), b, y.ptr<float>(), s);
+  mbc().a = x;
+  return y;
+}
+
+Tensor DepthwiseConv2D::backward(const Tensor& dy) {
+  const Tensor& x_ = mbc().a;
+  const ConvShape s = shape_for(x_.shape());
+  float* gw = params_[0].grad.ptr<float>();
+  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
+  if (dev_.is_gpu()) {
+    gpu_ops::dwconv_wgrad(dy.data(), x_.data(), gw, gb, s);
+    if (!input_grad_) return Tensor();
+    Tensor dx = act_empty(x_.shape(), dev_);
+    gpu_ops::dwconv_dgrad(dy.data(), params_[0].shadow.data(), dx.data(), s);
+    return dx;
+  }
+  Tensor dx = input_grad_ ? act_empty(x_.shape(), dev_) : Tensor();
+  cpu_ops::dwconv_bwd(x_.ptr<float>(), params_[0].value.ptr<float>(), dy.ptr<float>(),
+                      input_grad_ ? dx.ptr<float>() : nullptr, gw, gb, s);
+  return dx;
+}
+
 gpu_ops::BnbOperands BatchNorm::bnb_operands(int mb) {
   set_micro_batch(mb);
   MbCache& mc = mbc();
@@ -1193,6 +1284,10 @@ std::unique_ptr<Layer> create_layer(const json::Value& rec) {
     return std::make_unique<Conv2D>(I("in_channels", 0), I("out_channels", 0), I("kernel_h", 1), I("kernel_w", 1),
                                     I("stride_h", 1), I("stride_w", 1), I("pad_h", 0), I("pad_w", 0),
                                     p.get_bool("use_bias", true), name);
+  if (type == "depthwise_conv2d")
+    return std::make_unique<DepthwiseConv2D>(I("channels", 0), I("kernel_h", 1), I("kernel_w", 1), I("stride_h", 1),
+                                             I("stride_w", 1), I("pad_h", 0), I("pad_w", 0),
+                                             p.get_bool("use_bias", true), name);
   if (type == "dense")
     return std::make_unique<Dense>(I("input_features", 0), I("output_features", 0), p.get_bool("use_bias", true),
                                    name);
@@ -1559,6 +1654,17 @@ SequentialBuilder& SequentialBuilder::conv2d(int out_ch, int kh, int kw, int sh,
                                              const std::string& name) {
   if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
   auto l = std::make_unique<Conv2D>((int)cur_[0], out_ch, kh, kw, sh, sw, ph, pw, bias, auto_name(name, "conv2d"));
+  const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
+  cur_ = {o[1], o[2], o[3]};
+  model_.add(std::move(l));
+  return *this;
+}
+
+SequentialBuilder& SequentialBuilder::depthwise_conv2d(int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
+                                                       const std::string& name) {
+  if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
+  auto l = std::make_unique<DepthwiseConv2D>((int)cur_[0], kh, kw, sh, sw, ph, pw, bias,
+                                             auto_name(name, "depthwise_conv2d"));
   const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
   cur_ = {o[1], o[2], o[3]};
   model_.add(std::move(l));

@@ -17,6 +17,14 @@ void conv_bwd(const float* x, const float* w, const float* dy, float* dx, float*
   C::conv2d_bwd(x, w, dy, dx, dw, db, s.N, s.C, s.H, s.W, s.Co, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
 }
 
+void dwconv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s) {
+  C::depthwise_conv2d_fwd(x, w, b, y, s.N, s.C, s.H, s.W, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
+}
+
+void dwconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s) {
+  C::depthwise_conv2d_bwd(x, w, dy, dx, dw, db, s.N, s.C, s.H, s.W, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
+}
+
 void dense_fwd(const float* x, const float* w, const float* b, float* y, long N, long In, long Out) {
   C::dense_fwd(x, w, b, y, N, In, Out);
 }

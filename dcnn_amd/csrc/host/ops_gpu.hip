@@ -813,6 +813,36 @@ void conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvS
   wgrad_reduce(hold, bhold, slab, gw, (long)s.Co * Ng, bslab, gb, s.Co, splits);
 }
 
+// ---- depthwise conv (dwconv.hip): streaming kernels outside the routing table (route -1)
+namespace {
+DwArgs dw_args(const ConvShape& s, const char* what) {
+  if (s.Co != s.C) throw std::runtime_error(std::string(what) + ": depthwise conv needs Co == C");
+  return DwArgs{s.N, s.H, s.W, s.C, s.OH, s.OW, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW};
+}
+}  // namespace
+
+void dwconv_fwd(const void* x, const void* w, const float* bias, void* y, const ConvShape& s) {
+  rec("dw_fwd", s, -1, {{"bias", bias != nullptr}});
+  dcnn::dwconv_fwd(kBF16, x, w, bias, y, dw_args(s, "dwconv_fwd"), cur());
+}
+
+void dwconv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, const void* residual) {
+  rec("dw_dgrad", s, -1, {{"residual", residual != nullptr}});
+  dcnn::dwconv_dgrad(kBF16, dy, w, residual, dx, dw_args(s, "dwconv_dgrad"), cur());
+}
+
+void dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s) {
+  rec("dw_wgrad", s, -1, {{"bias", gb != nullptr}, {"deferred", g_defer}});
+  const DwArgs g = dw_args(s, "dwconv_wgrad");
+  const int splits = dcnn::dwconv_wgrad_splits(kBF16, g);
+  const long n = (long)s.C * s.KH * s.KW;
+  Tensor hold, bhold;
+  float* slab = wgrad_slab(SLAB, (size_t)splits * n * 4, hold);
+  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.C * 4, bhold) : nullptr;
+  dcnn::dwconv_wgrad(kBF16, dy, x, slab, bslab, g, cur());
+  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.C, splits);
+}
+
 bool stem_ok(const ConvShape& s) {
   return s.KH == 3 && s.KW == 3 && s.SH == 1 && s.SW == 1 && s.PH == 1 && s.PW == 1 &&
          stem_supported(s.N, s.C, s.H, s.W, s.Co);

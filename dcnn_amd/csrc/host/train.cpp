@@ -634,6 +634,26 @@ Sequential create_model(const std::string& name) {
       }
     return b.avgpool2d(4, 4, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(200, true, "fc").build();
   }
+  if (name == "mobilenet_v1_cifar10" || name == "mobilenet_v1_tiny_imagenet") {
+    // MobileNetV1 (models/zoo.py _mobilenet_v1: same layer names and order): stride-1 stem, 13
+    // depthwise-separable blocks, global average pool, classifier
+    const bool tiny = name == "mobilenet_v1_tiny_imagenet";
+    int hw = tiny ? 64 : 32;
+    SequentialBuilder b(tiny ? "MobileNetV1-Tiny-ImageNet" : "MobileNetV1-CIFAR10");
+    b.input({3, hw, hw}).conv2d(32, 3, 3, 1, 1, 1, 1, false, "conv1").batchnorm(1e-5f, 0.1f, true, "bn1")
+        .activation("relu", "relu1");
+    const int co[13] = {64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024};
+    const int st[13] = {1, 2, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1};
+    for (int i = 0; i < 13; ++i) {
+      const std::string k = std::to_string(i + 1);
+      b.depthwise_conv2d(3, 3, st[i], st[i], 1, 1, false, "dw" + k).batchnorm(1e-5f, 0.1f, true, "dw" + k + "_bn")
+          .activation("relu", "dw" + k + "_relu")
+          .conv2d(co[i], 1, 1, 1, 1, 0, 0, false, "pw" + k).batchnorm(1e-5f, 0.1f, true, "pw" + k + "_bn")
+          .activation("relu", "pw" + k + "_relu");
+      hw = (hw + 2 - 3) / st[i] + 1;
+    }
+    return b.avgpool2d(hw, hw, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(tiny ? 200 : 10, true, "fc").build();
+  }
   throw std::invalid_argument("unknown model '" + name + "'");
 }
 

@@ -61,6 +61,18 @@ struct T2Args {
 struct PoolGeom { int N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw; };
 // NHWC conv geometry of the explicit im2col path (im2col.hip)
 struct ConvGeom { int N, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW; };
+// depthwise conv (dwconv.hip; groups = C, channel multiplier 1): NHWC activations, weights [C][KH][KW]
+struct DwArgs { int N, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW; };
+// dt 0 fp32 / 1 bf16 (activations and weights; bias and slabs fp32). Supported: C % 4 (fp32) / % 8
+// (bf16) == 0, KH * KW <= 49, stride >= 1, pad < kernel, element offsets < 2^31; the launchers throw
+// on anything else. 3x3 / pad 1 / stride 1 or 2 run compile-time instances, the rest run-time taps.
+bool dwconv_supported(int dt, DwArgs g);
+void dwconv_fwd(int dt, const void* x, const void* w, const float* bias, void* y, DwArgs g, hipStream_t s);
+// gather form (no atomics): dx = conv^T(dy, w) (+ residual, a same-shape activation)
+void dwconv_dgrad(int dt, const void* dy, const void* w, const void* residual, void* dx, DwArgs g, hipStream_t s);
+// slab [splits][C * KH * KW] (+ bias_slab [splits][C], optional) for splitk_reduce*; splits as below
+int dwconv_wgrad_splits(int dt, DwArgs g);
+void dwconv_wgrad(int dt, const void* dy, const void* x, float* slab, float* bias_slab, DwArgs g, hipStream_t s);
 // halo-tiled stride-1 direct conv (hconv.hip): out[NB][H][W][N] = sum_t in[y+dy_t][x+dx_t][:] . B[n][tap_b_t + :]
 struct HConvArgs {
   const bf16* A; const bf16* B; bf16* C;

@@ -403,6 +403,29 @@ PYBIND11_MODULE(_kernels, m) {
            P<const float*>(mean), P<const float*>(istd), P<float*>(dg), P<float*>(db), P<float*>(aff), S(st));
   });
 
+  // depthwise conv (dwconv.hip): geometry as (N, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW)
+  m.def("dwconv_supported", [](int dt, std::array<int, 12> g) {
+    return dwconv_supported(dt, DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]});
+  });
+  m.def("dwconv_wgrad_splits", [](int dt, std::array<int, 12> g) {
+    return dwconv_wgrad_splits(dt, DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]});
+  });
+  m.def("dwconv_fwd", [](int dt, uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, std::array<int, 12> g,
+                         uintptr_t st) {
+    dwconv_fwd(dt, P<const void*>(x), P<const void*>(w), P<const float*>(bias), P<void*>(y),
+               DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]}, S(st));
+  });
+  m.def("dwconv_dgrad", [](int dt, uintptr_t dy, uintptr_t w, uintptr_t residual, uintptr_t dx, std::array<int, 12> g,
+                           uintptr_t st) {
+    dwconv_dgrad(dt, P<const void*>(dy), P<const void*>(w), P<const void*>(residual), P<void*>(dx),
+                 DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]}, S(st));
+  });
+  m.def("dwconv_wgrad", [](int dt, uintptr_t dy, uintptr_t x, uintptr_t slab, uintptr_t bslab, std::array<int, 12> g,
+                           uintptr_t st) {
+    dwconv_wgrad(dt, P<const void*>(dy), P<const void*>(x), P<float*>(slab), P<float*>(bslab),
+                 DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]}, S(st));
+  });
+
   auto geom = [](int N, int H, int W, int C, int OH, int OW, int ph, int pw, int sh, int sw, int padh, int padw) {
     return PoolGeom{N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw};
   };

@@ -476,6 +476,96 @@ void conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, int N,
   }
 }
 
+// ------------------------------------------------------------------ depthwise conv
+// groups = C, channel multiplier 1; w [C][KH][KW]. Direct loops over (n, c) planes (no im2col:
+// a plane's column matrix would be KH*KW times the plane for KH*KW MACs per element).
+template <typename T>
+void depthwise_conv2d_fwd(const T* x, const T* w, const T* bias, T* y, int N, int C, int H, int W, int KH, int KW,
+                          int SH, int SW, int PH, int PW) {
+  const int OH = out_dim(H, KH, SH, PH), OW = out_dim(W, KW, SW, PW);
+  parallel_for(0, (long)N * C, 1, [&](long lo, long hi) {
+    for (long t = lo; t < hi; ++t) {
+      const int c = (int)(t % C);
+      const T* xp = x + t * H * W;
+      const T* wp = w + (long)c * KH * KW;
+      T* yp = y + t * OH * OW;
+      const T bv = bias ? bias[c] : T(0);
+      for (int oy = 0; oy < OH; ++oy)
+        for (int ox = 0; ox < OW; ++ox) {
+          T s = bv;
+          for (int ky = 0; ky < KH; ++ky) {
+            const int iy = oy * SH + ky - PH;
+            if (iy < 0 || iy >= H) continue;
+            for (int kx = 0; kx < KW; ++kx) {
+              const int ix = ox * SW + kx - PW;
+              if (ix < 0 || ix >= W) continue;
+              s += wp[ky * KW + kx] * xp[(long)iy * W + ix];
+            }
+          }
+          yp[(long)oy * OW + ox] = s;
+        }
+    }
+  });
+}
+
+// dx (overwrite, may be null), dw += dW, db += sum dy (may be null). Each channel's parameter
+// gradients are summed by one task over samples then pixels in order (deterministic).
+template <typename T>
+void depthwise_conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, int N, int C, int H, int W, int KH,
+                          int KW, int SH, int SW, int PH, int PW) {
+  const int OH = out_dim(H, KH, SH, PH), OW = out_dim(W, KW, SW, PW);
+  const long KK = (long)KH * KW;
+  parallel_for(0, C, 1, [&](long lo, long hi) {
+    std::vector<double> acc(KK);
+    for (long c = lo; c < hi; ++c) {
+      std::fill(acc.begin(), acc.end(), 0.0);
+      double bs = 0.0;
+      for (long n = 0; n < N; ++n) {
+        const T* xp = x + (n * C + c) * H * W;
+        const T* gp = dy + (n * C + c) * OH * OW;
+        for (int oy = 0; oy < OH; ++oy)
+          for (int ox = 0; ox < OW; ++ox) {
+            const double g = gp[(long)oy * OW + ox];
+            bs += g;
+            for (int ky = 0; ky < KH; ++ky) {
+              const int iy = oy * SH + ky - PH;
+              if (iy < 0 || iy >= H) continue;
+              for (int kx = 0; kx < KW; ++kx) {
+                const int ix = ox * SW + kx - PW;
+                if (ix < 0 || ix >= W) continue;
+                acc[ky * KW + kx] += g * xp[(long)iy * W + ix];
+              }
+            }
+          }
+      }
+      for (long k = 0; k < KK; ++k) dw[c * KK + k] += (T)acc[k];
+      if (db) db[c] += (T)bs;
+    }
+  });
+  if (!dx) return;
+  parallel_for(0, (long)N * C, 1, [&](long lo, long hi) {
+    for (long t = lo; t < hi; ++t) {
+      const T* wp = w + (t % C) * KK;
+      const T* gp = dy + t * OH * OW;
+      T* dp = dx + t * H * W;
+      for (int iy = 0; iy < H; ++iy)
+        for (int ix = 0; ix < W; ++ix) {
+          T s = T(0);
+          for (int ky = 0; ky < KH; ++ky) {
+            const int ty = iy + PH - ky;
+            if (ty < 0 || ty % SH != 0 || ty / SH >= OH) continue;
+            for (int kx = 0; kx < KW; ++kx) {
+              const int tx = ix + PW - kx;
+              if (tx < 0 || tx % SW != 0 || tx / SW >= OW) continue;
+              s += wp[ky * KW + kx] * gp[(long)(ty / SH) * OW + tx / SW];
+            }
+          }
+          dp[(long)iy * W + ix] = s;
+        }
+    }
+  });
+}
+
 // ------------------------------------------------------------------ dense
 template <typename T>
 void dense_fwd(const T* x, const T* w, const T* bias, T* y, long N, long In, long Out) {
@@ -966,6 +1056,10 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
                               int);                                                                                 \
   template void conv2d_bwd<T>(const T*, const T*, const T*, T*, T*, T*, int, int, int, int, int, int, int, int, int, \
                               int, int);                                                                            \
+  template void depthwise_conv2d_fwd<T>(const T*, const T*, const T*, T*, int, int, int, int, int, int, int, int,   \
+                                        int, int);                                                                  \
+  template void depthwise_conv2d_bwd<T>(const T*, const T*, const T*, T*, T*, T*, int, int, int, int, int, int,     \
+                                        int, int, int, int);                                                        \
   template void dense_fwd<T>(const T*, const T*, const T*, T*, long, long, long);                                   \
   template void dense_bwd<T>(const T*, const T*, const T*, T*, T*, T*, long, long, long);                           \
   template void batchnorm_fwd<T>(const T*, T*, long, long, long, const T*, const T*, double, int, T*, T*, double,    \

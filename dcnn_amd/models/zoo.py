@@ -1,5 +1,6 @@
 """Model zoo: the 13 builders of the reference (`include/nn/example_models.hpp:13-437`),
-same layer sequence, names and hyper-parameters, so checkpoints are interchangeable.
+same layer sequence, names and hyper-parameters, so checkpoints are interchangeable; plus
+MobileNetV1 (Howard et al. 2017) on the depthwise layer, which the reference lacks.
 """
 from __future__ import annotations
 
@@ -172,6 +173,34 @@ def create_resnet50_imagenet() -> Sequential:
     return _resnet50_body(b).avgpool2d(7, 7, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(1000, True, "fc").build()
 
 
+# MobileNetV1 body: (pointwise output channels, depthwise stride) of the 13 separable blocks
+_MOBILENET_V1 = ((64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1), (512, 1), (512, 1), (512, 1),
+                 (512, 1), (1024, 2), (1024, 1))
+
+
+def _mobilenet_v1(name, hw, classes) -> Sequential:
+    """Stride-1 stem (the inputs are small; it rides the RGB stem kernel), 13 depthwise-separable
+    blocks dw3x3 -> BN -> ReLU -> 1x1 -> BN -> ReLU, global average pool, classifier. Layer names
+    and order match dcnn::create_model (train.cpp), so checkpoints interchange."""
+    b = (SequentialBuilder(name).input([3, hw, hw])
+         .conv2d(32, 3, 3, 1, 1, 1, 1, False, "conv1").batchnorm(1e-5, 0.1, True, "bn1").activation("relu", "relu1"))
+    for i, (co, s) in enumerate(_MOBILENET_V1, 1):
+        (b.depthwise_conv2d(3, 3, s, s, 1, 1, False, f"dw{i}").batchnorm(1e-5, 0.1, True, f"dw{i}_bn")
+         .activation("relu", f"dw{i}_relu")
+         .conv2d(co, 1, 1, 1, 1, 0, 0, False, f"pw{i}").batchnorm(1e-5, 0.1, True, f"pw{i}_bn")
+         .activation("relu", f"pw{i}_relu"))
+        hw = (hw + 2 - 3) // s + 1
+    return b.avgpool2d(hw, hw, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(classes, True, "fc").build()
+
+
+def create_mobilenet_v1_cifar10() -> Sequential:
+    return _mobilenet_v1("MobileNetV1-CIFAR10", 32, 10)
+
+
+def create_mobilenet_v1_tiny_imagenet() -> Sequential:
+    return _mobilenet_v1("MobileNetV1-Tiny-ImageNet", 64, 200)
+
+
 MODELS = {
     "mnist_cnn": create_mnist_trainer,
     "cifar10_cnn_v1": create_cifar10_trainer_v1,
@@ -186,6 +215,8 @@ MODELS = {
     "resnet34_tiny_imagenet": create_resnet34_tiny_imagenet,
     "resnet50_tiny_imagenet": create_resnet50_tiny_imagenet,
     "resnet50_imagenet": create_resnet50_imagenet,
+    "mobilenet_v1_cifar10": create_mobilenet_v1_cifar10,
+    "mobilenet_v1_tiny_imagenet": create_mobilenet_v1_tiny_imagenet,
 }
 
 INPUT_SHAPES = {
@@ -194,6 +225,7 @@ INPUT_SHAPES = {
     "resnet50_cifar10": (3, 32, 32), "resnet9_tiny_imagenet": (3, 64, 64), "cnn_tiny_imagenet": (3, 64, 64),
     "resnet18_tiny_imagenet": (3, 64, 64), "resnet34_tiny_imagenet": (3, 64, 64),
     "resnet50_tiny_imagenet": (3, 64, 64), "resnet50_imagenet": (3, 224, 224),
+    "mobilenet_v1_cifar10": (3, 32, 32), "mobilenet_v1_tiny_imagenet": (3, 64, 64),
 }
 
 NUM_CLASSES = {k: (10 if ("cifar" in k or "mnist" in k) else (1000 if k == "resnet50_imagenet" else 200))

@@ -172,6 +172,131 @@ class Conv2D(ParameterizedLayer):
                       cfg.name or "conv2d")
 
 
+class DepthwiseConv2D(ParameterizedLayer):
+    """Depthwise convolution: one KHxKW filter per channel (``F.conv2d(groups=C)``, channel
+    multiplier 1). Not in the reference. GPU path: the streaming kernels of dwconv.hip (no MFMA:
+    KH*KW MACs per element, bandwidth-bound). Deliberately not a :class:`Conv2D`: the fusion
+    planner sees it as ``FK_OTHER`` — it emits no BatchNorm statistics, ignores ``_bnb_request``
+    and needs no transposed weight operand."""
+    type_name = "depthwise_conv2d"
+
+    def __init__(self, channels: int, kernel_h: int, kernel_w: int, stride_h: int = 1, stride_w: int = 1,
+                 pad_h: int = 0, pad_w: int = 0, use_bias: bool = True, name: str = "depthwise_conv2d"):
+        super().__init__(name)
+        self.channels = int(channels)
+        self.kernel_h, self.kernel_w = int(kernel_h), int(kernel_w)
+        self.stride_h, self.stride_w = int(stride_h), int(stride_w)
+        self.pad_h, self.pad_w = int(pad_h), int(pad_w)
+        self.use_bias = bool(use_bias)
+
+    # params ---------------------------------------------------------------------------
+    def param_specs(self):
+        s = [ParamSpec("weights", (self.channels, 1, self.kernel_h, self.kernel_w))]
+        if self.use_bias:
+            s.append(ParamSpec("bias", (self.channels, 1, 1, 1)))
+        return s
+
+    def init_values(self, gen):
+        bound = 1.0 / math.sqrt(self.kernel_h * self.kernel_w)  # Conv2D's rule, fan-in of one channel
+        vals = [torch.empty((self.channels, 1, self.kernel_h, self.kernel_w)).uniform_(-bound, bound, generator=gen)]
+        if self.use_bias:
+            vals.append(torch.empty((self.channels, 1, 1, 1)).uniform_(-bound, bound, generator=gen))
+        return vals
+
+    @property
+    def weights(self):
+        return self._params[0]
+
+    @property
+    def bias(self):
+        return self._params[1] if self.use_bias else None
+
+    def _bias_vec(self):
+        return self._params[1].view(-1) if self.use_bias else None
+
+    def _sp(self):
+        return (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
+
+    # compute --------------------------------------------------------------------------
+    def forward(self, x, mb_id=0):
+        if not self.initialized:
+            raise RuntimeError(f"DepthwiseConv2D '{self.name}' must be initialized before forward")
+        x = self._to_layer_device(x)
+        if x.shape[1] != self.channels:
+            raise ValueError(f"DepthwiseConv2D '{self.name}': input has {x.shape[1]} channels, expected "
+                             f"{self.channels}")
+        st, pd = self._sp()
+        if x.is_cuda:
+            from ...ops import hip
+            xa = hip.to_act(x, self.compute_dtype)
+            y = hip.dwconv2d_fwd(xa, self.weight_operand(0), self._bias_vec(), st, pd)
+            self._cache[mb_id] = xa
+            return y
+        from ...ops import cpu
+        y = cpu.depthwise_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd)
+        self._cache[mb_id] = x
+        return y
+
+    def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
+        x = self._cache.pop(mb_id, None)
+        if x is None:
+            raise RuntimeError(f"DepthwiseConv2D '{self.name}': no cached input for micro-batch {mb_id}")
+        grad = grad.to(x.device)
+        st, pd = self._sp()
+        gb = self._grads[1].view(-1) if self.use_bias else None
+        if x.is_cuda:
+            from ...ops import hip
+            g = hip.to_act(grad, self.compute_dtype)
+            hip.dwconv2d_wgrad(g, x, self.weights.shape, st, pd, self._grads[0], gb)
+            if not self.needs_input_grad:
+                return None
+            res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
+            return hip.dwconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, residual=res)
+        from ...ops import cpu
+        dx = cpu.depthwise_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self._grads[0], gb,
+                                      need_dx=self.needs_input_grad)
+        if dx is not None and add_to is not None:
+            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
+        return dx
+
+    # shapes / cost ----------------------------------------------------------------------
+    def _out_hw(self, h, w):
+        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
+                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
+
+    def compute_output_shape(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        return [s[0], self.channels, oh, ow]
+
+    def forward_flops(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        out = s[0] * oh * ow
+        f = 2 * self.channels * self.kernel_h * self.kernel_w * out
+        if self.use_bias:
+            f += self.channels * out
+        return f
+
+    def backward_flops(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        out = s[0] * oh * ow
+        f = 4 * self.channels * self.kernel_h * self.kernel_w * out  # weight grad + input grad
+        if self.use_bias:
+            f += self.channels * out
+        return f
+
+    def get_config(self):
+        return LayerConfig(self.name, dict(
+            channels=self.channels, kernel_h=self.kernel_h, kernel_w=self.kernel_w, stride_h=self.stride_h,
+            stride_w=self.stride_w, pad_h=self.pad_h, pad_w=self.pad_w, use_bias=self.use_bias), self.type_name)
+
+    @staticmethod
+    def from_config(cfg):
+        p = cfg.parameters
+        return DepthwiseConv2D(p["channels"], p["kernel_h"], p["kernel_w"], p.get("stride_h", 1),
+                               p.get("stride_w", 1), p.get("pad_h", 0), p.get("pad_w", 0), p.get("use_bias", True),
+                               cfg.name or "depthwise_conv2d")
+
+
 class Dense(ParameterizedLayer):
     type_name = "dense"
 

@@ -14,7 +14,7 @@ import torch
 
 from ..activations import ActivationFactory
 from .base import LayerConfig, Layer, run_backward
-from .conv import Conv2D
+from .conv import Conv2D, DepthwiseConv2D
 from .misc import Activation, MaxPool2D
 from .norm import BatchNorm
 
@@ -215,6 +215,8 @@ class ResidualBlock(Layer):
                     return first.backward(g, mb_id, add_to=d_s)
                 finally:
                     first._bnb_request = None
+            if isinstance(first, DepthwiseConv2D):
+                return first.backward(g, mb_id, add_to=d_s)  # dF + dS in the dgrad's store
             return first.backward(g, mb_id) + d_s
         pre, out = ent
         g = self.act.gradient(pre, out, grad) if self.act is not None else grad

@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from ..device import Device, DeviceType, get_cpu, get_device
-from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, Dropout, Flatten, GroupNorm, Layer,
-                     LayerBuilder, LayerConfig, LayerFactory, MaxPool2D, ParameterizedLayer, ResidualBlock,
+from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten, GroupNorm,
+                     Layer, LayerBuilder, LayerConfig, LayerFactory, MaxPool2D, ParameterizedLayer, ResidualBlock,
                      create_layer, plan_fusion)
 from .layers.base import run_backward
 from .params import ParamArena
@@ -669,6 +669,10 @@ class SequentialBuilder:
                name=""):
         return self._add(Conv2D(self._shape[1], out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                 use_bias, self._n(name, "conv2d")))
+
+    def depthwise_conv2d(self, kernel_h, kernel_w, stride_h=1, stride_w=1, pad_h=0, pad_w=0, use_bias=True, name=""):
+        return self._add(DepthwiseConv2D(self._shape[1], kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                                         use_bias, self._n(name, "depthwise_conv2d")))
 
     def dense(self, output_features, use_bias=True, name=""):
         feat = 1

@@ -207,6 +207,41 @@ def conv2d_bwd(x, w, dy, stride, pad, grad_w, grad_b=None, need_dx=True):
     return dx
 
 
+def depthwise_conv2d_fwd(x, w, bias, stride, pad):
+    """Depthwise conv (groups = C, multiplier 1): w (C,1,KH,KW), bias [C] or None."""
+    x, w, bias = _c(x), _c(w), _c(bias)
+    _same(x, w, bias)
+    N, Cc, H, W = x.shape
+    C2, one, KH, KW = w.shape
+    if C2 != Cc or one != 1:
+        raise ValueError(f"depthwise_conv2d: {Cc} input channels, weights {tuple(w.shape)} (expected ({Cc}, 1, KH, KW))")
+    OH, OW = _odim(H, KH, stride[0], pad[0]), _odim(W, KW, stride[1], pad[1])
+    if OH < 1 or OW < 1:
+        raise ValueError(f"depthwise_conv2d: kernel {KH}x{KW} does not fit the padded {H}x{W} input")
+    y = torch.empty((N, Cc, OH, OW), dtype=x.dtype)
+    C().depthwise_conv2d_fwd(dt(x), x.data_ptr(), w.data_ptr(), p(bias), y.data_ptr(), N, Cc, H, W, KH, KW, stride[0],
+                             stride[1], pad[0], pad[1])
+    return y
+
+
+def depthwise_conv2d_bwd(x, w, dy, stride, pad, grad_w, grad_b=None, need_dx=True):
+    """grad_w += dW, grad_b += sum(dy); returns dx (or None). grad_w/grad_b must be contiguous."""
+    x, w, dy = _c(x), _c(w), _c(dy)
+    _same(x, w, dy, grad_w, grad_b)
+    N, Cc, H, W = x.shape
+    _, _, KH, KW = w.shape
+    OH, OW = _odim(H, KH, stride[0], pad[0]), _odim(W, KW, stride[1], pad[1])
+    if tuple(w.shape[:2]) != (Cc, 1) or tuple(dy.shape) != (N, Cc, OH, OW):
+        raise ValueError(f"depthwise_conv2d_bwd: x {tuple(x.shape)}, w {tuple(w.shape)}, dy {tuple(dy.shape)}")
+    for g in (grad_w, grad_b):
+        if g is not None and not g.is_contiguous():
+            raise ValueError("gradient accumulators must be contiguous")
+    dx = torch.empty_like(x) if need_dx else None
+    C().depthwise_conv2d_bwd(dt(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), p(dx), grad_w.data_ptr(), p(grad_b), N,
+                             Cc, H, W, KH, KW, stride[0], stride[1], pad[0], pad[1])
+    return dx
+
+
 def dense_fwd(x2d, w2d, bias):
     x2d, w2d, bias = _c(x2d), _c(w2d), _c(bias)
     _same(x2d, w2d, bias)
