@@ -8,6 +8,11 @@ ResNet-18-tiny layer shapes. Reports device time per call and achieved TFLOP/s.
 shapes instead — per pass the device time, the compulsory GB/s, a plain device copy moving the
 same number of bytes, PyTorch's F.conv2d(groups=C) passes (bf16 channels_last) and, with --step,
 the captured training step of mobilenet_v1_tiny_imagenet on the Python engine.
+
+--grouped: the grouped-conv MFMA kernels (gconv.hip) at the ResNeXt-50-32x4d-Tiny-ImageNet shapes,
+same method — against a same-bytes copy, PyTorch's F.conv2d(groups=32) passes and the project's own
+dense conv at the same channel counts, with the percentage of the bf16 MFMA peak the issued FLOPs
+reach and, with --step, the captured training step of resnext50_32x4d_tiny_imagenet.
 """
 import argparse
 import os
@@ -178,6 +183,125 @@ def depthwise_main(a):
             json.dump(dict(batch=N, iters=a.iters, reps=a.reps, rows=rows, step=step), f, indent=1)
 
 
+# every distinct grouped (C = Ci = Co, H, W, stride, layers of that shape) of
+# resnext50_32x4d_tiny_imagenet (3x3, pad 1, 32 groups: 4, 8, 16 and 32 channels per group)
+SHAPES_GC = [(128, 32, 32, 1, 3), (256, 32, 32, 2, 1), (256, 16, 16, 1, 3), (512, 16, 16, 2, 1), (512, 8, 8, 1, 5),
+             (1024, 8, 8, 2, 1), (1024, 4, 4, 1, 2)]
+GC_GROUPS = 32
+MFMA_BF16_PEAK = 2.5e15  # dense bf16 FLOP/s of the chip (datasheet)
+
+
+def _gc_issued_flops(N, C, G, H, W, OH, OW, T):
+    """MFMA FLOPs the gconv.hip kernels issue (their tiling, bundle and zero-tap padding included)
+    per pass, next to the useful 2 * pixels * C * (C / G) * T."""
+    cg = C // G
+    bundle = 1 if cg >= 16 else 16 // cg
+    steps = -(-(T * -(-(bundle * cg) // 8)) // 4)          # 32-deep k-steps per 16-channel tile
+    cpad = -(-C // 16) * 16
+    fd = lambda pix: 2.0 * (-(-pix // 64) * 64) * cpad * 32 * steps  # noqa: E731
+    nct = -(-(bundle * cg) // 16)
+    wg = 2.0 * (-(-N * OH * OW // 32) * 32) * 16 * 16 * (cpad // 16) * nct * T
+    return {"fwd": fd(N * OH * OW), "dgrad": fd(N * H * W), "wgrad": wg}
+
+
+def grouped_main(a):
+    import json
+    import torch.nn.functional as F
+    from dcnn_amd.ops import hip
+    CL = torch.channels_last
+    N, G = a.batch, GC_GROUPS
+    rows = []
+    print(f"{'shape':<18}{'op':<7}{'us':>9}{'min':>9}{'max':>9}{'copy us':>9}{'% copy':>8}{'% peak':>8}{'pad x':>7}"
+          f"{'torch us':>10}{'torch/ours':>11}{'dense us':>10}{'dense/ours':>11}")
+    for (C, H, W, s, count) in SHAPES_GC:
+        OH, OW = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+        cg = C // G
+        x = torch.randn(N, C, H, W, device="cuda").bfloat16().contiguous(memory_format=CL)
+        w = (torch.randn(C, cg, 3, 3, device="cuda") / (9 * cg) ** 0.5).bfloat16().contiguous(memory_format=CL)
+        dy = torch.randn(N, C, OH, OW, device="cuda").bfloat16().contiguous(memory_format=CL)
+        gw = torch.zeros(C, cg, 3, 3, device="cuda").contiguous(memory_format=CL)
+        # the project's dense conv at the same channel counts (G times the arithmetic and weight bytes)
+        wd = (torch.randn(C, C, 3, 3, device="cuda") / (9 * C) ** 0.5).bfloat16().contiguous(memory_format=CL)
+        wdt = hip.conv_weight_t(wd, dtype=torch.bfloat16)
+        gwd = torch.zeros(C, C, 3, 3, device="cuda").contiguous(memory_format=CL)
+        xb, yb = 2.0 * N * H * W * C, 2.0 * N * OH * OW * C
+        # compulsory bytes: each activation read or written once (weights and slabs are < 1 %)
+        hbm = {"fwd": xb + yb, "dgrad": xb + yb, "wgrad": xb + yb}
+        useful = 2.0 * N * OH * OW * C * cg * 9
+        issued = _gc_issued_flops(N, C, G, H, W, OH, OW, 9)
+        ops = {"fwd": lambda: hip.gconv2d_fwd(x, w, None, (s, s), (1, 1), G),
+               "dgrad": lambda: hip.gconv2d_dgrad(dy, w, tuple(x.shape), (s, s), (1, 1), G),
+               "wgrad": lambda: hip.gconv2d_wgrad(dy, x, tuple(w.shape), (s, s), (1, 1), G, gw, None)}
+        dops = {"fwd": lambda: hip.conv2d_fwd(x, wd, None, (s, s), (1, 1)),
+                "dgrad": lambda: hip.conv2d_dgrad(dy, wdt, tuple(x.shape), (s, s), (1, 1)),
+                "wgrad": lambda: hip.conv2d_wgrad(dy, x, tuple(wd.shape), (s, s), (1, 1), gwd, None)}
+        aten = torch.ops.aten.convolution_backward
+        bwd = lambda mask: aten(dy, x, w, None, [s, s], [1, 1], [1, 1], False, [0, 0], G, mask)  # noqa: E731
+        tops = {"fwd": lambda: F.conv2d(x, w, None, s, 1, groups=G),
+                "dgrad": lambda: bwd([True, False, False]), "wgrad": lambda: bwd([False, True, False])}
+        for op, fn in ops.items():
+            if a.only and op != a.only:
+                continue
+            us, lo, hi, _ = _time_graph(fn, a.iters, a.reps)
+            # a flat copy moving the same bytes (half of them read, half written)
+            n = int(hbm[op] / 2) // 2
+            src, dst = torch.empty(n, device="cuda", dtype=torch.bfloat16), torch.empty(n, device="cuda", dtype=torch.bfloat16)
+            cus, _, _, _ = _time_graph(lambda: dst.copy_(src), a.iters, a.reps)
+            del src, dst
+            dus, _, _, _ = _time_graph(dops[op], a.iters, a.reps)
+            tus, tmode = float("nan"), "-"
+            if a.torch_ref:
+                tus, _, _, tmode = _time_graph(tops[op], a.iters, a.reps)
+            r = dict(C=C, G=G, H=H, W=W, stride=s, layers=count, op=op, us=us, us_min=lo, us_max=hi, copy_us=cus,
+                     pct_copy=100.0 * cus / us, issued_flops=issued[op], useful_flops=useful,
+                     pct_peak=100.0 * issued[op] / (us * 1e-6) / MFMA_BF16_PEAK, torch_us=tus, torch_mode=tmode,
+                     torch_over_ours=tus / us, dense_us=dus, dense_over_ours=dus / us)
+            rows.append(r)
+            print(f"{f'c{C} {H}x{W} s{s}':<18}{op:<7}{us:9.1f}{lo:9.1f}{hi:9.1f}{cus:9.1f}{r['pct_copy']:8.1f}"
+                  f"{r['pct_peak']:8.2f}{issued[op] / useful:7.1f}{tus:10.1f}{tus / us:11.2f}{dus:10.1f}{dus / us:11.2f}",
+                  flush=True)
+            if a.json:
+                with open(a.json, "w") as f:
+                    json.dump(dict(batch=N, iters=a.iters, reps=a.reps, rows=rows), f, indent=1)
+    step = None
+    if a.step:
+        from dcnn_amd.models import create_model
+        from dcnn_amd.nn import Adam, LossFactory
+        from dcnn_amd.runtime.step import TrainStep
+        m = create_model("resnext50_32x4d_tiny_imagenet")
+        m.set_seed(1)
+        m.set_device("GPU:0")
+        m.initialize()
+        m.set_first_layer_input_grad(False)
+        opt = Adam(1e-3)
+        opt.attach(m)
+        st = TrainStep(m, LossFactory.create("softmax_crossentropy"), opt, use_graph=True)
+        xs = torch.randn(N, 3, 64, 64, device="cuda")
+        ys = torch.randint(0, 200, (N,), device="cuda")
+        for _ in range(6):
+            st(xs, ys)
+        torch.cuda.synchronize()
+        ms = []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(a.reps):
+            e0.record()
+            for _ in range(20):
+                st(xs, ys)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / 20)
+        ms.sort()
+        # the grouped launches' share: the table's per-pass medians times the layers of each shape
+        gc_ms = sum(r["us"] * r["layers"] for r in rows) / 1000.0
+        step = dict(model="resnext50_32x4d_tiny_imagenet", batch=N, graph=st.graphs is not None,
+                    ms=ms[len(ms) // 2], ms_min=ms[0], ms_max=ms[-1], img_s=N * 1000.0 / ms[len(ms) // 2],
+                    loss=float(st.last_loss.item()), grouped_ms=gc_ms, grouped_share=gc_ms / ms[len(ms) // 2])
+        print("training step:", step, flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(batch=N, iters=a.iters, reps=a.reps, rows=rows, step=step), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -202,9 +326,14 @@ def main():
     ap.add_argument("--torch-ref", type=int, default=1, help="--depthwise: also time PyTorch's grouped conv passes")
     ap.add_argument("--step", action="store_true", help="--depthwise: also time the captured MobileNetV1 training step")
     ap.add_argument("--json", default="", help="--depthwise: write the figures to this file as they come")
+    ap.add_argument("--grouped", action="store_true",
+                    help="grouped-conv kernels at the ResNeXt-50 32x4d tiny shapes (takes --reps, --torch-ref, --step, "
+                         "--json like --depthwise)")
     a = ap.parse_args()
     if a.depthwise:
         return depthwise_main(a)
+    if a.grouped:
+        return grouped_main(a)
     from dcnn_amd.ops import hip, fusion
     if a.split_target is not None:
         hip.kernels().hconv_set_split_target(a.split_target)

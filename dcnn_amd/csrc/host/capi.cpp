@@ -123,6 +123,31 @@ int dcnn_c_dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, con
   });
 }
 
+// grouped conv (groups: the extra argument): y = gconv(x, w) + bias, w bf16 [Co][KH][KW][C / groups]
+int dcnn_c_gconv_fwd(const void* x, const void* w, const float* bias, void* y, const int* shape, int groups) {
+  return guarded([&] { gpu_ops::gconv_fwd(x, w, bias, y, shape_of(shape), groups); });
+}
+
+// dx = gconv^T(dy, w) (+ residual)
+int dcnn_c_gconv_dgrad(const void* dy, const void* w, void* dx, const int* shape, int groups, const void* residual) {
+  return guarded([&] { gpu_ops::gconv_dgrad(dy, w, dx, shape_of(shape), groups, residual); });
+}
+
+// gw / gb (+=) the weight / bias gradient; deferred: inside a backward's batched split-K reduce
+int dcnn_c_gconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const int* shape, int groups,
+                       int deferred) {
+  return guarded([&] {
+    if (deferred) gpu_ops::begin_deferred_reduce();
+    try {
+      gpu_ops::gconv_wgrad(dy, x, gw, gb, shape_of(shape), groups);
+    } catch (...) {
+      if (deferred) gpu_ops::end_deferred_reduce();
+      throw;
+    }
+    if (deferred) gpu_ops::end_deferred_reduce();
+  });
+}
+
 int dcnn_c_stem_fwd(const float* x, const void* w, const float* bias, void* y, const int* shape, int want_stats,
                     const float** slab, int* rows) {
   return guarded([&] {

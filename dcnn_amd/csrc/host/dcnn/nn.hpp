@@ -180,6 +180,30 @@ class DepthwiseConv2D : public Layer {
   bool bias_;
 };
 
+// Grouped convolution (1 < groups < channels): weights (Co, Ci / G, KH, KW). Not a Conv2D: the fusion
+// planner sees FK_OTHER (no statistics epilogue, no backward-BatchNorm fusion); the data gradient
+// can add a residual (the shortcut gradient of a block whose main path starts with it) in its store.
+class GroupedConv2D : public Layer {
+ public:
+  GroupedConv2D(int in_ch, int out_ch, int kh, int kw, int groups, int sh = 1, int sw = 1, int ph = 0, int pw = 0,
+                bool bias = true, std::string name = "grouped_conv2d");
+  std::string type() const override { return "grouped_conv2d"; }
+  json::Value parameters_config() const override;
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override;
+  Tensor backward(const Tensor& dy) override;
+  // dx = conv^T(dy) + residual (GPU): wgrad + the fused data gradient
+  Tensor backward_residual(const Tensor& dy, const Tensor& residual);
+  double flops(const std::vector<int64_t>& in) const override;
+
+ private:
+  ConvShape shape_for(const std::vector<int64_t>& in) const;
+  Tensor backward_impl(const Tensor& dy, const Tensor* residual);
+  int ci_, co_, kh_, kw_, g_, sh_, sw_, ph_, pw_;
+  bool bias_;
+};
+
 class Dense : public Layer {
  public:
   Dense(int in_features, int out_features, bool bias = true, std::string name = "dense");
@@ -472,6 +496,8 @@ class SequentialBuilder {
   // channels from the running shape
   SequentialBuilder& depthwise_conv2d(int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0, bool bias = true,
                                       const std::string& name = "");
+  SequentialBuilder& grouped_conv2d(int out_ch, int kh, int kw, int groups, int sh = 1, int sw = 1, int ph = 0,
+                                    int pw = 0, bool bias = true, const std::string& name = "");
   SequentialBuilder& batchnorm(float eps = 1e-5f, float momentum = 0.1f, bool affine = true,
                                const std::string& name = "");
   SequentialBuilder& activation(const std::string& kind = "relu", const std::string& name = "");
@@ -492,6 +518,8 @@ class SequentialBuilder {
   // 1x1-BN-ReLU-3x3(stride)-BN-ReLU-1x1-BN, BN eps 1e-3 (reference include/nn/sequential.hpp:1288)
   SequentialBuilder& bottleneck_residual_block(int in_ch, int mid_ch, int out_ch, int stride = 1,
                                                const std::string& name = "");
+  SequentialBuilder& resnext_bottleneck_block(int in_ch, int mid_ch, int out_ch, int groups, int stride = 1,
+                                              const std::string& name = "");
   Sequential build();
 
  private:

@@ -21,6 +21,10 @@ void conv_bwd(const float* x, const float* w, const float* dy, float* dx, float*
 // depthwise conv (groups = C, channel multiplier 1; s.Co == s.C): w [C][KH][KW]; dx may be null
 void dwconv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s);
 void dwconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s);
+// grouped conv (1 < G < C): w [Co][C / G][KH][KW]; dx may be null, dw / db accumulate
+void gconv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s, int groups);
+void gconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s,
+               int groups);
 void dense_fwd(const float* x, const float* w, const float* b, float* y, long N, long In, long Out);
 void dense_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, long N, long In,
                long Out);
@@ -109,6 +113,14 @@ void conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvS
 void dwconv_fwd(const void* x, const void* w, const float* bias, void* y, const ConvShape& s);
 void dwconv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, const void* residual = nullptr);
 void dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s);
+// grouped conv (gconv.hip): bf16 NHWC activations, w bf16 [Co][KH][KW][C / G], bias fp32 or null; a
+// shape the kernels do not take throws. dgrad: dx = conv^T(dy, w) (+ residual), the transposed
+// operand made from w by one small launch; wgrad: gw fp32 [Co][KH][KW][C / G] and gb fp32 [Co]
+// accumulate (+=) through wgrad_slab / wgrad_reduce
+void gconv_fwd(const void* x, const void* w, const float* bias, void* y, const ConvShape& s, int groups);
+void gconv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, int groups,
+                 const void* residual = nullptr);
+void gconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s, int groups);
 // the network's first conv straight from the fp32 NCHW input (RGB stem kernel: <= 4 input
 // channels, 3x3 stride-1 'same', 16-multiple outputs up to 64); y bf16 NHWC
 bool stem_ok(const ConvShape& s);

@@ -337,6 +337,117 @@ Tensor DepthwiseConv2D::backward(const Tensor& dy) {
   return dx;
 }
 
+// ------------------------------------------------------------------ GroupedConv2D
+GroupedConv2D::GroupedConv2D(int in_ch, int out_ch, int kh, int kw, int groups, int sh, int sw, int ph, int pw,
+                             bool bias, std::string name)
+    : Layer(std::move(name)), ci_(in_ch), co_(out_ch), kh_(kh), kw_(kw), g_(groups), sh_(sh), sw_(sw), ph_(ph),
+      pw_(pw), bias_(bias) {
+  if (g_ == 1) throw std::invalid_argument(name_ + ": groups == 1, use Conv2D");
+  if (g_ == ci_ && g_ == co_)
+    throw std::invalid_argument(name_ + ": groups == in == out channels, use DepthwiseConv2D");
+  if (g_ < 1 || ci_ % g_ != 0 || co_ % g_ != 0)
+    throw std::invalid_argument(name_ + ": groups " + std::to_string(g_) + " must divide in_channels " +
+                                std::to_string(ci_) + " and out_channels " + std::to_string(co_));
+}
+
+json::Value GroupedConv2D::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["in_channels"] = ci_;
+  p["out_channels"] = co_;
+  p["kernel_h"] = kh_;
+  p["kernel_w"] = kw_;
+  p["groups"] = g_;
+  p["stride_h"] = sh_;
+  p["stride_w"] = sw_;
+  p["pad_h"] = ph_;
+  p["pad_w"] = pw_;
+  p["use_bias"] = bias_;
+  return p;
+}
+
+ConvShape GroupedConv2D::shape_for(const std::vector<int64_t>& in) const {
+  ConvShape s{};
+  s.N = (int)in[0];
+  s.C = (int)in[1];
+  s.H = (int)in[2];
+  s.W = (int)in[3];
+  s.Co = co_;
+  s.KH = kh_;
+  s.KW = kw_;
+  s.SH = sh_;
+  s.SW = sw_;
+  s.PH = ph_;
+  s.PW = pw_;
+  s.OH = (s.H + 2 * ph_ - kh_) / sh_ + 1;
+  s.OW = (s.W + 2 * pw_ - kw_) / sw_ + 1;
+  if (s.C != ci_) throw std::runtime_error(name_ + ": input has " + std::to_string(s.C) + " channels, expected " +
+                                           std::to_string(ci_));
+  return s;
+}
+
+std::vector<int64_t> GroupedConv2D::output_shape(const std::vector<int64_t>& in) const {
+  const ConvShape s = shape_for(in);
+  return {in[0], co_, s.OH, s.OW};
+}
+
+void GroupedConv2D::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+  (void)in;
+  dev_ = dev;
+  params_.clear();
+  const int cig = ci_ / g_;
+  const float bound = 1.f / std::sqrt((float)(cig * kh_ * kw_));  // Conv2D's rule, one group's fan-in
+  // GPU: physical [Co][KH][KW][Ci / G] (the MFMA operand); CPU: NCHW
+  const Layout wl = dev.is_gpu() ? Layout::NHWC : Layout::NCHW;
+  add_param("weights", {co_, cig, kh_, kw_}, wl, uniform_init((size_t)co_ * cig * kh_ * kw_, bound, seed));
+  if (bias_) add_param("bias", {co_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)co_, bound, seed + 1));
+}
+
+double GroupedConv2D::flops(const std::vector<int64_t>& in) const {
+  const ConvShape s = shape_for(in);
+  const double out = (double)s.N * s.OH * s.OW, k = (double)(ci_ / g_) * kh_ * kw_;  // a dense conv's / G
+  return 6.0 * co_ * k * out + (bias_ ? 2.0 * co_ * out : 0.0);  // forward 2, backward 4 per MAC
+}
+
+Tensor GroupedConv2D::forward(const Tensor& x, bool training) {
+  (void)training;
+  check_act(x, dev_, "grouped_conv2d");
+  const ConvShape s = shape_for(x.shape());
+  Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
+  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
+  if (dev_.is_gpu())
+    gpu_ops::gconv_fwd(x.data(), params_[0].shadow.data(), b, y.data(), s, g_);
+  else
+    cpu_ops::gconv_fwd(x.ptr<float>(), params_[0].value.ptr<float>(), b, y.ptr<float>(), s, g_);
+  mbc().a = x;
+  return y;
+}
+
+Tensor GroupedConv2D::backward_impl(const Tensor& dy, const Tensor* residual) {
+  const Tensor& x_ = mbc().a;
+  const ConvShape s = shape_for(x_.shape());
+  float* gw = params_[0].grad.ptr<float>();
+  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
+  if (dev_.is_gpu()) {
+    gpu_ops::gconv_wgrad(dy.data(), x_.data(), gw, gb, s, g_);
+    if (!input_grad_ && residual == nullptr) return Tensor();
+    Tensor dx = act_empty(x_.shape(), dev_);
+    gpu_ops::gconv_dgrad(dy.data(), params_[0].shadow.data(), dx.data(), s, g_, residual ? residual->data() : nullptr);
+    return dx;
+  }
+  Tensor dx = input_grad_ ? act_empty(x_.shape(), dev_) : Tensor();
+  cpu_ops::gconv_bwd(x_.ptr<float>(), params_[0].value.ptr<float>(), dy.ptr<float>(),
+                     input_grad_ ? dx.ptr<float>() : nullptr, gw, gb, s, g_);
+  return dx;
+}
+
+Tensor GroupedConv2D::backward(const Tensor& dy) { return backward_impl(dy, nullptr); }
+
+Tensor GroupedConv2D::backward_residual(const Tensor& dy, const Tensor& residual) {
+  if (!dev_.is_gpu() || residual.shape() != mbc().a.shape())
+    throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
+  return backward_impl(dy, &residual);
+}
+
 gpu_ops::BnbOperands BatchNorm::bnb_operands(int mb) {
   set_micro_batch(mb);
   MbCache& mc = mbc();
@@ -1092,6 +1203,9 @@ Tensor ResidualBlock::backward(const Tensor& dy) {
     // the main path's first conv adds the shortcut gradient in its data-gradient epilogue
     auto* head = dynamic_cast<Conv2D*>(main_[0].get());
     if (head != nullptr && input_grad_ && gs.defined() && gs.dtype() == DType::BF16) return head->backward_residual(gm, gs);
+    auto* ghead = dynamic_cast<GroupedConv2D*>(main_[0].get());
+    if (ghead != nullptr && main_.size() > 1 && input_grad_ && gs.defined() && gs.dtype() == DType::BF16)
+      return ghead->backward_residual(gm, gs);
     gm = main_[0]->backward(gm);
     if (!gm.defined() || !gs.defined()) return Tensor();
     Tensor dx = act_empty(gm.shape(), dev_);
@@ -1288,6 +1402,10 @@ std::unique_ptr<Layer> create_layer(const json::Value& rec) {
     return std::make_unique<DepthwiseConv2D>(I("channels", 0), I("kernel_h", 1), I("kernel_w", 1), I("stride_h", 1),
                                              I("stride_w", 1), I("pad_h", 0), I("pad_w", 0),
                                              p.get_bool("use_bias", true), name);
+  if (type == "grouped_conv2d")
+    return std::make_unique<GroupedConv2D>(I("in_channels", 0), I("out_channels", 0), I("kernel_h", 1),
+                                           I("kernel_w", 1), I("groups", 1), I("stride_h", 1), I("stride_w", 1),
+                                           I("pad_h", 0), I("pad_w", 0), p.get_bool("use_bias", true), name);
   if (type == "dense")
     return std::make_unique<Dense>(I("input_features", 0), I("output_features", 0), p.get_bool("use_bias", true),
                                    name);
@@ -1671,6 +1789,17 @@ SequentialBuilder& SequentialBuilder::depthwise_conv2d(int kh, int kw, int sh, i
   return *this;
 }
 
+SequentialBuilder& SequentialBuilder::grouped_conv2d(int out_ch, int kh, int kw, int groups, int sh, int sw, int ph,
+                                                     int pw, bool bias, const std::string& name) {
+  if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
+  auto l = std::make_unique<GroupedConv2D>((int)cur_[0], out_ch, kh, kw, groups, sh, sw, ph, pw, bias,
+                                           auto_name(name, "grouped_conv2d"));
+  const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
+  cur_ = {o[1], o[2], o[3]};
+  model_.add(std::move(l));
+  return *this;
+}
+
 SequentialBuilder& SequentialBuilder::batchnorm(float eps, float momentum, bool affine, const std::string& name) {
   model_.add(std::make_unique<BatchNorm>((int)cur_.at(0), eps, momentum, affine, auto_name(name, "batchnorm")));
   return *this;
@@ -1765,6 +1894,27 @@ SequentialBuilder& SequentialBuilder::bottleneck_residual_block(int in_ch, int m
   }
   return residual(std::move(m), std::move(sc), "relu",
                   name.empty() ? "bottleneck_residual_block_" + std::to_string(model_.layers().size()) : name);
+}
+
+// bottleneck_residual_block with the 3x3 replaced by a grouped conv (Xie et al. 2017)
+SequentialBuilder& SequentialBuilder::resnext_bottleneck_block(int in_ch, int mid_ch, int out_ch, int groups,
+                                                               int stride, const std::string& name) {
+  std::vector<std::unique_ptr<Layer>> m, sc;
+  m.push_back(std::make_unique<Conv2D>(in_ch, mid_ch, 1, 1, 1, 1, 0, 0, false, "conv2d_0"));
+  m.push_back(std::make_unique<BatchNorm>(mid_ch, 1e-3f, 0.1f, true, "bn0"));
+  m.push_back(std::make_unique<Activation>("relu", "relu_0"));
+  m.push_back(std::make_unique<GroupedConv2D>(mid_ch, mid_ch, 3, 3, groups, stride, stride, 1, 1, false,
+                                              "grouped_conv2d_1"));
+  m.push_back(std::make_unique<BatchNorm>(mid_ch, 1e-3f, 0.1f, true, "bn0"));
+  m.push_back(std::make_unique<Activation>("relu", "relu_1"));
+  m.push_back(std::make_unique<Conv2D>(mid_ch, out_ch, 1, 1, 1, 1, 0, 0, false, "conv2d_2"));
+  m.push_back(std::make_unique<BatchNorm>(out_ch, 1e-3f, 0.1f, true, "bn0"));
+  if (stride != 1 || in_ch != out_ch) {
+    sc.push_back(std::make_unique<Conv2D>(in_ch, out_ch, 1, 1, stride, stride, 0, 0, false, "conv2d_0"));
+    sc.push_back(std::make_unique<BatchNorm>(out_ch, 1e-3f, 0.1f, true, "bn0"));
+  }
+  return residual(std::move(m), std::move(sc), "relu",
+                  name.empty() ? "resnext_bottleneck_block_" + std::to_string(model_.layers().size()) : name);
 }
 
 Sequential SequentialBuilder::build() { return std::move(model_); }

@@ -25,6 +25,15 @@ void dwconv_bwd(const float* x, const float* w, const float* dy, float* dx, floa
   C::depthwise_conv2d_bwd(x, w, dy, dx, dw, db, s.N, s.C, s.H, s.W, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
 }
 
+void gconv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s, int groups) {
+  C::grouped_conv2d_fwd(x, w, b, y, s.N, s.C, s.H, s.W, s.Co, groups, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
+}
+
+void gconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s,
+               int groups) {
+  C::grouped_conv2d_bwd(x, w, dy, dx, dw, db, s.N, s.C, s.H, s.W, s.Co, groups, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW);
+}
+
 void dense_fwd(const float* x, const float* w, const float* b, float* y, long N, long In, long Out) {
   C::dense_fwd(x, w, b, y, N, In, Out);
 }

@@ -843,6 +843,39 @@ void dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const Con
   wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.C, splits);
 }
 
+// ---- grouped conv (gconv.hip): MFMA kernels outside the routing table (route -1)
+namespace {
+GcArgs gc_args(const ConvShape& s, int groups) {
+  return GcArgs{s.N, s.H, s.W, s.C, s.Co, groups, s.OH, s.OW, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW};
+}
+}  // namespace
+
+void gconv_fwd(const void* x, const void* w, const float* bias, void* y, const ConvShape& s, int groups) {
+  rec("gc_fwd", s, -1, {{"bias", bias != nullptr}});
+  dcnn::gconv_fwd(kBF16, x, w, bias, y, gc_args(s, groups), cur());
+}
+
+void gconv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, int groups, const void* residual) {
+  rec("gc_dgrad", s, -1, {{"residual", residual != nullptr}});
+  const GcArgs g = gc_args(s, groups);
+  if (!dcnn::gconv_supported(kBF16, g)) throw std::invalid_argument("gconv_dgrad: unsupported grouped conv shape");
+  void* wt = scratch(W_T, (size_t)s.C * s.KH * s.KW * (s.Co / groups) * 2);
+  dcnn::gconv_weight_t(kBF16, w, wt, g, cur());
+  dcnn::gconv_dgrad(kBF16, dy, wt, residual, dx, g, cur());
+}
+
+void gconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s, int groups) {
+  rec("gc_wgrad", s, -1, {{"bias", gb != nullptr}, {"deferred", g_defer}});
+  const GcArgs g = gc_args(s, groups);
+  const int splits = dcnn::gconv_wgrad_splits(kBF16, g);
+  const long n = (long)s.Co * s.KH * s.KW * (s.C / groups);
+  Tensor hold, bhold;
+  float* slab = wgrad_slab(SLAB, (size_t)splits * n * 4, hold);
+  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
+  dcnn::gconv_wgrad(kBF16, dy, x, slab, bslab, g, cur());
+  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.Co, splits);
+}
+
 bool stem_ok(const ConvShape& s) {
   return s.KH == 3 && s.KW == 3 && s.SH == 1 && s.SW == 1 && s.PH == 1 && s.PW == 1 &&
          stem_supported(s.N, s.C, s.H, s.W, s.Co);

@@ -654,6 +654,27 @@ Sequential create_model(const std::string& name) {
     }
     return b.avgpool2d(hw, hw, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(tiny ? 200 : 10, true, "fc").build();
   }
+  if (name == "resnext50_32x4d_tiny_imagenet" || name == "resnext26_32x4d_cifar10") {
+    // ResNeXt 32x4d (models/zoo.py _resnext_body: same layer names and order): bottleneck blocks
+    // 1x1 -> grouped 3x3 (32 groups) -> 1x1, widths 128 / 256 / 512 / 1024 -> 256 / ... / 2048
+    const bool tiny = name == "resnext50_32x4d_tiny_imagenet";
+    SequentialBuilder b(tiny ? "ResNeXt-50-32x4d-Tiny-ImageNet" : "ResNeXt-26-32x4d-CIFAR10");
+    if (tiny)
+      b.input({3, 64, 64}).conv2d(64, 3, 3, 1, 1, 1, 1, true, "conv1").batchnorm(1e-5f, 0.1f, true, "bn1")
+          .activation("relu", "relu1").maxpool2d(3, 3, 2, 2, 1, 1, "maxpool");
+    else
+      b.input({3, 32, 32}).conv2d(64, 3, 3, 1, 1, 1, 1, false, "conv1").batchnorm(1e-5f, 0.1f, true, "bn1")
+          .activation("relu", "relu1");
+    const int blocks50[4] = {3, 4, 6, 3}, blocks26[4] = {2, 2, 2, 2}, mid[4] = {128, 256, 512, 1024};
+    int in = 64;
+    for (int L = 0; L < 4; ++L)
+      for (int i = 1; i <= (tiny ? blocks50 : blocks26)[L]; ++i) {
+        b.resnext_bottleneck_block(in, mid[L], 2 * mid[L], 32, (i == 1 && L > 0) ? 2 : 1,
+                                   "layer" + std::to_string(L + 1) + "_block" + std::to_string(i));
+        in = 2 * mid[L];
+      }
+    return b.avgpool2d(4, 4, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(tiny ? 200 : 10, true, "fc").build();
+  }
   throw std::invalid_argument("unknown model '" + name + "'");
 }
 

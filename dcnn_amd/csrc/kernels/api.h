@@ -73,6 +73,21 @@ void dwconv_dgrad(int dt, const void* dy, const void* w, const void* residual, v
 // slab [splits][C * KH * KW] (+ bias_slab [splits][C], optional) for splitk_reduce*; splits as below
 int dwconv_wgrad_splits(int dt, DwArgs g);
 void dwconv_wgrad(int dt, const void* dy, const void* x, float* slab, float* bias_slab, DwArgs g, hipStream_t s);
+// grouped conv (gconv.hip; 1 < G < C): NHWC activations, weights [Co][KH][KW][Ci / G] (channels_last)
+struct GcArgs { int N, H, W, Ci, Co, G, OH, OW, KH, KW, SH, SW, PH, PW; };
+// dt 0 fp32 / 1 bf16 (activations and weights; bias and slabs fp32), MFMA implicit GEMMs, one launch
+// per pass over all groups. Supported: G >= 2 dividing Ci and Co, Ci / G and Co / G each in {4, 8, 16}
+// or a multiple of 32, KH * KW <= 49, stride >= 1, pad < kernel, element offsets < 2^31; the
+// launchers throw std::invalid_argument on anything else.
+bool gconv_supported(int dt, GcArgs g);
+void gconv_fwd(int dt, const void* x, const void* w, const float* bias, void* y, GcArgs g, hipStream_t s);
+// wt [Ci][KH][KW][Co / G]: the data gradient's operand, from w
+void gconv_weight_t(int dt, const void* w, void* wt, GcArgs g, hipStream_t s);
+// gather form (no atomics): dx = conv^T(dy, w) (+ residual, a same-shape activation); takes wt
+void gconv_dgrad(int dt, const void* dy, const void* wt, const void* residual, void* dx, GcArgs g, hipStream_t s);
+// slab [splits][Co * KH * KW * Ci / G] (+ bias_slab [splits][Co], optional) for splitk_reduce*
+int gconv_wgrad_splits(int dt, GcArgs g);
+void gconv_wgrad(int dt, const void* dy, const void* x, float* slab, float* bias_slab, GcArgs g, hipStream_t s);
 // halo-tiled stride-1 direct conv (hconv.hip): out[NB][H][W][N] = sum_t in[y+dy_t][x+dx_t][:] . B[n][tap_b_t + :]
 struct HConvArgs {
   const bf16* A; const bf16* B; bf16* C;

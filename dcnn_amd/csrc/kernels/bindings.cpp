@@ -426,6 +426,28 @@ PYBIND11_MODULE(_kernels, m) {
                  DwArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]}, S(st));
   });
 
+  // grouped conv (gconv.hip): geometry as (N, H, W, Ci, Co, G, OH, OW, KH, KW, SH, SW, PH, PW)
+  auto gc = [](const std::array<int, 14>& g) {
+    return GcArgs{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13]};
+  };
+  m.def("gconv_supported", [gc](int dt, std::array<int, 14> g) { return gconv_supported(dt, gc(g)); });
+  m.def("gconv_wgrad_splits", [gc](int dt, std::array<int, 14> g) { return gconv_wgrad_splits(dt, gc(g)); });
+  m.def("gconv_fwd", [gc](int dt, uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, std::array<int, 14> g,
+                          uintptr_t st) {
+    gconv_fwd(dt, P<const void*>(x), P<const void*>(w), P<const float*>(bias), P<void*>(y), gc(g), S(st));
+  });
+  m.def("gconv_weight_t", [gc](int dt, uintptr_t w, uintptr_t wt, std::array<int, 14> g, uintptr_t st) {
+    gconv_weight_t(dt, P<const void*>(w), P<void*>(wt), gc(g), S(st));
+  });
+  m.def("gconv_dgrad", [gc](int dt, uintptr_t dy, uintptr_t wt, uintptr_t residual, uintptr_t dx,
+                            std::array<int, 14> g, uintptr_t st) {
+    gconv_dgrad(dt, P<const void*>(dy), P<const void*>(wt), P<const void*>(residual), P<void*>(dx), gc(g), S(st));
+  });
+  m.def("gconv_wgrad", [gc](int dt, uintptr_t dy, uintptr_t x, uintptr_t slab, uintptr_t bslab,
+                            std::array<int, 14> g, uintptr_t st) {
+    gconv_wgrad(dt, P<const void*>(dy), P<const void*>(x), P<float*>(slab), P<float*>(bslab), gc(g), S(st));
+  });
+
   auto geom = [](int N, int H, int W, int C, int OH, int OW, int ph, int pw, int sh, int sw, int padh, int padw) {
     return PoolGeom{N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw};
   };

@@ -99,6 +99,17 @@ void bind_cpu(py::module_& parent) {
     DT_DISPATCH(dt, depthwise_conv2d_bwd<T>(P<const T>(x), P<const T>(w), P<const T>(dy), P<T>(dx), P<T>(dw), P<T>(db),
                                             N, C, H, W, KH, KW, SH, SW, PH, PW));
   }, Rel());
+  m.def("grouped_conv2d_fwd", [](int dt, uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int N, int C, int H,
+                                 int W, int Co, int G, int KH, int KW, int SH, int SW, int PH, int PW) {
+    DT_DISPATCH(dt, grouped_conv2d_fwd<T>(P<const T>(x), P<const T>(w), P<const T>(bias), P<T>(y), N, C, H, W, Co, G,
+                                          KH, KW, SH, SW, PH, PW));
+  }, Rel());
+  m.def("grouped_conv2d_bwd", [](int dt, uintptr_t x, uintptr_t w, uintptr_t dy, uintptr_t dx, uintptr_t dw,
+                                 uintptr_t db, int N, int C, int H, int W, int Co, int G, int KH, int KW, int SH,
+                                 int SW, int PH, int PW) {
+    DT_DISPATCH(dt, grouped_conv2d_bwd<T>(P<const T>(x), P<const T>(w), P<const T>(dy), P<T>(dx), P<T>(dw), P<T>(db),
+                                          N, C, H, W, Co, G, KH, KW, SH, SW, PH, PW));
+  }, Rel());
   m.def("dense_fwd", [](int dt, uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, long N, long In, long Out) {
     DT_DISPATCH(dt, dense_fwd<T>(P<const T>(x), P<const T>(w), P<const T>(bias), P<T>(y), N, In, Out));
   }, Rel());

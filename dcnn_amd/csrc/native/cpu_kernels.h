@@ -43,6 +43,13 @@ void depthwise_conv2d_fwd(const T* x, const T* w, const T* bias, T* y, int N, in
 template <typename T>
 void depthwise_conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, int N, int C, int H, int W, int KH,
                           int KW, int SH, int SW, int PH, int PW);
+// grouped (1 < G < C): w [Co][C / G][KH][KW]; bwd: dx overwritten (may be null), dw / db +=
+template <typename T>
+void grouped_conv2d_fwd(const T* x, const T* w, const T* bias, T* y, int N, int C, int H, int W, int Co, int G, int KH,
+                        int KW, int SH, int SW, int PH, int PW);
+template <typename T>
+void grouped_conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, int N, int C, int H, int W, int Co,
+                        int G, int KH, int KW, int SH, int SW, int PH, int PW);
 template <typename T> void dense_fwd(const T* x, const T* w, const T* bias, T* y, long N, long In, long Out);
 template <typename T>
 void dense_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, long N, long In, long Out);

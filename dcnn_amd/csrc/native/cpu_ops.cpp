@@ -566,6 +566,112 @@ void depthwise_conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* 
   });
 }
 
+// ------------------------------------------------------------------ grouped conv
+// 1 < groups < C: w [Co][Cig][KH][KW], output channel co reads the Cig = C / G input channels of
+// group co / (Co / G). Direct loops over (n, channel) planes, the innermost one a contiguous run
+// of a row (per-group im2col would rebuild the columns once per group for K = Cig KH KW MACs).
+template <typename T>
+void grouped_conv2d_fwd(const T* x, const T* w, const T* bias, T* y, int N, int C, int H, int W, int Co, int G, int KH,
+                        int KW, int SH, int SW, int PH, int PW) {
+  const int OH = out_dim(H, KH, SH, PH), OW = out_dim(W, KW, SW, PW);
+  const int Cig = C / G, Cog = Co / G;
+  parallel_for(0, (long)N * Co, 1, [&](long lo, long hi) {
+    for (long t = lo; t < hi; ++t) {
+      const long n = t / Co;
+      const int co = (int)(t % Co), g = co / Cog;
+      T* yp = y + t * OH * OW;
+      const T bv = bias ? bias[co] : T(0);
+      for (long i = 0; i < (long)OH * OW; ++i) yp[i] = bv;
+      for (int cl = 0; cl < Cig; ++cl) {
+        const T* xp = x + (n * C + (long)g * Cig + cl) * H * W;
+        const T* wp = w + ((long)co * Cig + cl) * KH * KW;
+        for (int ky = 0; ky < KH; ++ky)
+          for (int kx = 0; kx < KW; ++kx) {
+            const T wv = wp[ky * KW + kx];
+            for (int oy = 0; oy < OH; ++oy) {
+              const int iy = oy * SH + ky - PH;
+              if (iy < 0 || iy >= H) continue;
+              const T* xr = xp + (long)iy * W;
+              T* yr = yp + (long)oy * OW;
+              for (int ox = 0; ox < OW; ++ox) {
+                const int ix = ox * SW + kx - PW;
+                if (ix >= 0 && ix < W) yr[ox] += wv * xr[ix];
+              }
+            }
+          }
+      }
+    }
+  });
+}
+
+// dx (overwrite, may be null), dw += dW, db += sum dy (may be null). Each output channel's
+// parameter gradients are summed by one task over samples then pixels in order (deterministic);
+// each (n, input channel) plane of dx is written by one task.
+template <typename T>
+void grouped_conv2d_bwd(const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, int N, int C, int H, int W, int Co,
+                        int G, int KH, int KW, int SH, int SW, int PH, int PW) {
+  const int OH = out_dim(H, KH, SH, PH), OW = out_dim(W, KW, SW, PW);
+  const int Cig = C / G, Cog = Co / G;
+  const long KK = (long)KH * KW;
+  parallel_for(0, Co, 1, [&](long lo, long hi) {
+    for (long co = lo; co < hi; ++co) {
+      const long g = co / Cog;
+      if (db) {
+        double bs = 0.0;
+        for (long n = 0; n < N; ++n) {
+          const T* gp = dy + (n * Co + co) * OH * OW;
+          for (long i = 0; i < (long)OH * OW; ++i) bs += gp[i];
+        }
+        db[co] += (T)bs;
+      }
+      for (int cl = 0; cl < Cig; ++cl)
+        for (int ky = 0; ky < KH; ++ky)
+          for (int kx = 0; kx < KW; ++kx) {
+            double acc = 0.0;
+            for (long n = 0; n < N; ++n) {
+              const T* xp = x + (n * C + g * Cig + cl) * H * W;
+              const T* gp = dy + (n * Co + co) * OH * OW;
+              for (int oy = 0; oy < OH; ++oy) {
+                const int iy = oy * SH + ky - PH;
+                if (iy < 0 || iy >= H) continue;
+                for (int ox = 0; ox < OW; ++ox) {
+                  const int ix = ox * SW + kx - PW;
+                  if (ix >= 0 && ix < W) acc += (double)gp[(long)oy * OW + ox] * xp[(long)iy * W + ix];
+                }
+              }
+            }
+            dw[(co * Cig + cl) * KK + ky * KW + kx] += (T)acc;
+          }
+    }
+  });
+  if (!dx) return;
+  parallel_for(0, (long)N * C, 1, [&](long lo, long hi) {
+    for (long t = lo; t < hi; ++t) {
+      const long n = t / C;
+      const int ci = (int)(t % C), g = ci / Cig, cl = ci - g * Cig;
+      T* dp = dx + t * H * W;
+      for (long i = 0; i < (long)H * W; ++i) dp[i] = T(0);
+      for (int j = 0; j < Cog; ++j) {
+        const long co = (long)g * Cog + j;
+        const T* gp = dy + (n * Co + co) * OH * OW;
+        const T* wp = w + (co * Cig + cl) * KK;
+        for (int ky = 0; ky < KH; ++ky)
+          for (int kx = 0; kx < KW; ++kx) {
+            const T wv = wp[ky * KW + kx];
+            for (int oy = 0; oy < OH; ++oy) {
+              const int iy = oy * SH + ky - PH;
+              if (iy < 0 || iy >= H) continue;
+              for (int ox = 0; ox < OW; ++ox) {
+                const int ix = ox * SW + kx - PW;
+                if (ix >= 0 && ix < W) dp[(long)iy * W + ix] += wv * gp[(long)oy * OW + ox];
+              }
+            }
+          }
+      }
+    }
+  });
+}
+
 // ------------------------------------------------------------------ dense
 template <typename T>
 void dense_fwd(const T* x, const T* w, const T* bias, T* y, long N, long In, long Out) {
@@ -1060,6 +1166,10 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
                                         int, int);                                                                  \
   template void depthwise_conv2d_bwd<T>(const T*, const T*, const T*, T*, T*, T*, int, int, int, int, int, int,     \
                                         int, int, int, int);                                                        \
+  template void grouped_conv2d_fwd<T>(const T*, const T*, const T*, T*, int, int, int, int, int, int, int, int,     \
+                                      int, int, int, int);                                                          \
+  template void grouped_conv2d_bwd<T>(const T*, const T*, const T*, T*, T*, T*, int, int, int, int, int, int, int,   \
+                                      int, int, int, int, int);                                                     \
   template void dense_fwd<T>(const T*, const T*, const T*, T*, long, long, long);                                   \
   template void dense_bwd<T>(const T*, const T*, const T*, T*, T*, T*, long, long, long);                           \
   template void batchnorm_fwd<T>(const T*, T*, long, long, long, const T*, const T*, double, int, T*, T*, double,    \

@@ -1,6 +1,7 @@
 """Model zoo: the 13 builders of the reference (`include/nn/example_models.hpp:13-437`),
 same layer sequence, names and hyper-parameters, so checkpoints are interchangeable; plus
-MobileNetV1 (Howard et al. 2017) on the depthwise layer, which the reference lacks.
+MobileNetV1 (Howard et al. 2017) on the depthwise layer and ResNeXt (Xie et al. 2017) on
+the grouped layer, which the reference lacks.
 """
 from __future__ import annotations
 
@@ -201,6 +202,37 @@ def create_mobilenet_v1_tiny_imagenet() -> Sequential:
     return _mobilenet_v1("MobileNetV1-Tiny-ImageNet", 64, 200)
 
 
+# ResNeXt 32x4d: (grouped width, output width) per stage; the grouped 3x3 has 32 groups
+_RESNEXT_WIDTHS = ((128, 256), (256, 512), (512, 1024), (1024, 2048))
+
+
+def _resnext_body(b: SequentialBuilder, blocks, groups=32) -> SequentialBuilder:
+    """Stages of bottleneck blocks 1x1 -> grouped 3x3 -> 1x1 (stride on the grouped conv of each
+    stage's first block but the first stage's). With 32 groups the four stages have 4, 8, 16 and 32
+    channels per group."""
+    cin = 64
+    for s, (n, (mid, out)) in enumerate(zip(blocks, _RESNEXT_WIDTHS), 1):
+        for i in range(1, n + 1):
+            b.resnext_bottleneck_block(cin, mid, out, groups, 2 if (i == 1 and s > 1) else 1, f"layer{s}_block{i}")
+            cin = out
+    return b
+
+
+def create_resnext50_32x4d_tiny_imagenet() -> Sequential:
+    b = (SequentialBuilder("ResNeXt-50-32x4d-Tiny-ImageNet").input([3, 64, 64])
+         .conv2d(64, 3, 3, 1, 1, 1, 1, True, "conv1").batchnorm(1e-5, 0.1, True, "bn1")
+         .activation("relu", "relu1").maxpool2d(3, 3, 2, 2, 1, 1, "maxpool"))
+    return (_resnext_body(b, (3, 4, 6, 3)).avgpool2d(4, 4, 1, 1, 0, 0, "avgpool").flatten("flatten")
+            .dense(200, True, "fc").build())
+
+
+def create_resnext26_32x4d_cifar10() -> Sequential:
+    b = (SequentialBuilder("ResNeXt-26-32x4d-CIFAR10").input([3, 32, 32])
+         .conv2d(64, 3, 3, 1, 1, 1, 1, False, "conv1").batchnorm(1e-5, 0.1, True, "bn1").activation("relu", "relu1"))
+    return (_resnext_body(b, (2, 2, 2, 2)).avgpool2d(4, 4, 1, 1, 0, 0, "avgpool").flatten("flatten")
+            .dense(10, True, "fc").build())
+
+
 MODELS = {
     "mnist_cnn": create_mnist_trainer,
     "cifar10_cnn_v1": create_cifar10_trainer_v1,
@@ -217,6 +249,8 @@ MODELS = {
     "resnet50_imagenet": create_resnet50_imagenet,
     "mobilenet_v1_cifar10": create_mobilenet_v1_cifar10,
     "mobilenet_v1_tiny_imagenet": create_mobilenet_v1_tiny_imagenet,
+    "resnext50_32x4d_tiny_imagenet": create_resnext50_32x4d_tiny_imagenet,
+    "resnext26_32x4d_cifar10": create_resnext26_32x4d_cifar10,
 }
 
 INPUT_SHAPES = {
@@ -226,6 +260,7 @@ INPUT_SHAPES = {
     "resnet18_tiny_imagenet": (3, 64, 64), "resnet34_tiny_imagenet": (3, 64, 64),
     "resnet50_tiny_imagenet": (3, 64, 64), "resnet50_imagenet": (3, 224, 224),
     "mobilenet_v1_cifar10": (3, 32, 32), "mobilenet_v1_tiny_imagenet": (3, 64, 64),
+    "resnext50_32x4d_tiny_imagenet": (3, 64, 64), "resnext26_32x4d_cifar10": (3, 32, 32),
 }
 
 NUM_CLASSES = {k: (10 if ("cifar" in k or "mnist" in k) else (1000 if k == "resnet50_imagenet" else 200))

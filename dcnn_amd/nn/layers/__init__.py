@@ -6,7 +6,7 @@ from __future__ import annotations
 from typing import Callable, Dict, List, Optional
 
 from .base import Layer, LayerConfig, ParameterizedLayer, StatelessLayer
-from .conv import Conv2D, Dense, DepthwiseConv2D
+from .conv import Conv2D, Dense, DepthwiseConv2D, GroupedConv2D
 from .misc import Activation, AvgPool2D, Dropout, Flatten, MaxPool2D
 from .norm import BatchNorm, GroupNorm
 from .residual import ResidualBlock, plan_fusion
@@ -21,8 +21,8 @@ class LayerFactory:
 
     @classmethod
     def register_defaults(cls) -> None:
-        for L in (Dense, Conv2D, DepthwiseConv2D, Activation, MaxPool2D, AvgPool2D, Dropout, BatchNorm, GroupNorm,
-                  Flatten, ResidualBlock):
+        for L in (Dense, Conv2D, DepthwiseConv2D, GroupedConv2D, Activation, MaxPool2D, AvgPool2D, Dropout, BatchNorm,
+                  GroupNorm, Flatten, ResidualBlock):
             cls.register_layer(L.type_name, L.from_config)
 
     @classmethod
@@ -97,6 +97,12 @@ class LayerBuilder:
         return self.add_layer(DepthwiseConv2D(s[1], kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, use_bias,
                                               self._auto(name, "depthwise_conv2d")))
 
+    def grouped_conv2d(self, out_channels, kernel_h, kernel_w, groups, stride_h=1, stride_w=1, pad_h=0, pad_w=0,
+                       use_bias=True, name=""):
+        s = self.get_current_shape()
+        return self.add_layer(GroupedConv2D(s[1], out_channels, kernel_h, kernel_w, groups, stride_h, stride_w, pad_h,
+                                            pad_w, use_bias, self._auto(name, "grouped_conv2d")))
+
     def batchnorm(self, epsilon=1e-5, momentum=0.1, affine=True, name=""):
         s = self.get_current_shape()
         return self.add_layer(BatchNorm(s[1], epsilon, momentum, affine, self._auto(name, "batchnorm")))
@@ -131,6 +137,6 @@ def residual_block(main_path, shortcut_path, activation="relu", name="residual_b
     return ResidualBlock(main_path, shortcut_path, activation, name)
 
 
-__all__ = ["Layer", "LayerConfig", "ParameterizedLayer", "StatelessLayer", "Conv2D", "DepthwiseConv2D", "Dense",
+__all__ = ["Layer", "LayerConfig", "ParameterizedLayer", "StatelessLayer", "Conv2D", "DepthwiseConv2D", "GroupedConv2D", "Dense",
            "BatchNorm", "GroupNorm", "MaxPool2D", "AvgPool2D", "Dropout", "Flatten", "Activation", "ResidualBlock",
            "LayerFactory", "LayerBuilder", "create_layer", "residual_block", "plan_fusion"]

@@ -297,6 +297,147 @@ class DepthwiseConv2D(ParameterizedLayer):
                                cfg.name or "depthwise_conv2d")
 
 
+class GroupedConv2D(ParameterizedLayer):
+    """Grouped convolution, 1 < groups < channels (``F.conv2d(groups=G)``): output channel co reads
+    the ``in_channels / groups`` input channels of group ``co // (out_channels / groups)``. Not in
+    the reference. GPU path: the MFMA implicit-GEMM kernels of gconv.hip, one launch per pass over
+    all groups. A separate class like :class:`DepthwiseConv2D`: the fusion planner sees it as
+    ``FK_OTHER`` — it emits no BatchNorm statistics and ignores ``_bnb_request``."""
+    type_name = "grouped_conv2d"
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_h: int, kernel_w: int, groups: int,
+                 stride_h: int = 1, stride_w: int = 1, pad_h: int = 0, pad_w: int = 0, use_bias: bool = True,
+                 name: str = "grouped_conv2d"):
+        super().__init__(name)
+        self.in_channels, self.out_channels, self.groups = int(in_channels), int(out_channels), int(groups)
+        self.kernel_h, self.kernel_w = int(kernel_h), int(kernel_w)
+        self.stride_h, self.stride_w = int(stride_h), int(stride_w)
+        self.pad_h, self.pad_w = int(pad_h), int(pad_w)
+        self.use_bias = bool(use_bias)
+        if self.groups == 1:
+            raise ValueError(f"GroupedConv2D '{name}': groups == 1, use Conv2D")
+        if self.groups == self.in_channels == self.out_channels:
+            raise ValueError(f"GroupedConv2D '{name}': groups == in_channels == out_channels == {self.groups}, "
+                             f"use DepthwiseConv2D")
+        if self.groups < 1 or self.in_channels % self.groups or self.out_channels % self.groups:
+            raise ValueError(f"GroupedConv2D '{name}': groups {self.groups} must divide in_channels "
+                             f"{self.in_channels} and out_channels {self.out_channels}")
+
+    # params ---------------------------------------------------------------------------
+    def _wshape(self):
+        return (self.out_channels, self.in_channels // self.groups, self.kernel_h, self.kernel_w)
+
+    def param_specs(self):
+        s = [ParamSpec("weights", self._wshape(), True)]
+        if self.use_bias:
+            s.append(ParamSpec("bias", (self.out_channels, 1, 1, 1)))
+        return s
+
+    def init_values(self, gen):
+        fan_in = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # Conv2D's rule, one group's fan-in
+        bound = 1.0 / math.sqrt(fan_in)
+        vals = [torch.empty(self._wshape()).uniform_(-bound, bound, generator=gen)]
+        if self.use_bias:
+            vals.append(torch.empty((self.out_channels, 1, 1, 1)).uniform_(-bound, bound, generator=gen))
+        return vals
+
+    @property
+    def weights(self):
+        return self._params[0]
+
+    @property
+    def bias(self):
+        return self._params[1] if self.use_bias else None
+
+    def _bias_vec(self):
+        return self._params[1].view(-1) if self.use_bias else None
+
+    def _sp(self):
+        return (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
+
+    # compute --------------------------------------------------------------------------
+    def forward(self, x, mb_id=0):
+        if not self.initialized:
+            raise RuntimeError(f"GroupedConv2D '{self.name}' must be initialized before forward")
+        x = self._to_layer_device(x)
+        if x.shape[1] != self.in_channels:
+            raise ValueError(f"GroupedConv2D '{self.name}': input has {x.shape[1]} channels, expected "
+                             f"{self.in_channels}")
+        st, pd = self._sp()
+        if x.is_cuda:
+            from ...ops import hip
+            xa = hip.to_act(x, self.compute_dtype)
+            y = hip.gconv2d_fwd(xa, self.weight_operand(0), self._bias_vec(), st, pd, self.groups)
+            self._cache[mb_id] = xa
+            return y
+        from ...ops import cpu
+        y = cpu.grouped_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd, self.groups)
+        self._cache[mb_id] = x
+        return y
+
+    def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
+        x = self._cache.pop(mb_id, None)
+        if x is None:
+            raise RuntimeError(f"GroupedConv2D '{self.name}': no cached input for micro-batch {mb_id}")
+        grad = grad.to(x.device)
+        st, pd = self._sp()
+        gb = self._grads[1].view(-1) if self.use_bias else None
+        if x.is_cuda:
+            from ...ops import hip
+            g = hip.to_act(grad, self.compute_dtype)
+            hip.gconv2d_wgrad(g, x, self.weights.shape, st, pd, self.groups, self._grads[0], gb)
+            if not self.needs_input_grad:
+                return None
+            res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
+            return hip.gconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, self.groups, residual=res)
+        from ...ops import cpu
+        dx = cpu.grouped_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self.groups, self._grads[0], gb,
+                                    need_dx=self.needs_input_grad)
+        if dx is not None and add_to is not None:
+            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
+        return dx
+
+    # shapes / cost ----------------------------------------------------------------------
+    def _out_hw(self, h, w):
+        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
+                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
+
+    def compute_output_shape(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        return [s[0], self.out_channels, oh, ow]
+
+    def forward_flops(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        out = s[0] * oh * ow
+        k = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # a dense conv's, divided by G
+        f = 2 * self.out_channels * k * out
+        if self.use_bias:
+            f += self.out_channels * out
+        return f
+
+    def backward_flops(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        out = s[0] * oh * ow
+        k = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w
+        f = 4 * self.out_channels * k * out  # weight grad + input grad
+        if self.use_bias:
+            f += self.out_channels * out
+        return f
+
+    def get_config(self):
+        return LayerConfig(self.name, dict(
+            in_channels=self.in_channels, out_channels=self.out_channels, kernel_h=self.kernel_h,
+            kernel_w=self.kernel_w, groups=self.groups, stride_h=self.stride_h, stride_w=self.stride_w,
+            pad_h=self.pad_h, pad_w=self.pad_w, use_bias=self.use_bias), self.type_name)
+
+    @staticmethod
+    def from_config(cfg):
+        p = cfg.parameters
+        return GroupedConv2D(p["in_channels"], p["out_channels"], p["kernel_h"], p["kernel_w"], p["groups"],
+                             p.get("stride_h", 1), p.get("stride_w", 1), p.get("pad_h", 0), p.get("pad_w", 0),
+                             p.get("use_bias", True), cfg.name or "grouped_conv2d")
+
+
 class Dense(ParameterizedLayer):
     type_name = "dense"
 

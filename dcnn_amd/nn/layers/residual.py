@@ -14,7 +14,7 @@ import torch
 
 from ..activations import ActivationFactory
 from .base import LayerConfig, Layer, run_backward
-from .conv import Conv2D, DepthwiseConv2D
+from .conv import Conv2D, DepthwiseConv2D, GroupedConv2D
 from .misc import Activation, MaxPool2D
 from .norm import BatchNorm
 
@@ -215,7 +215,7 @@ class ResidualBlock(Layer):
                     return first.backward(g, mb_id, add_to=d_s)
                 finally:
                     first._bnb_request = None
-            if isinstance(first, DepthwiseConv2D):
+            if isinstance(first, (DepthwiseConv2D, GroupedConv2D)):
                 return first.backward(g, mb_id, add_to=d_s)  # dF + dS in the dgrad's store
             return first.backward(g, mb_id) + d_s
         pre, out = ent

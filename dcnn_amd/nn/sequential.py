@@ -29,8 +29,8 @@ import torch
 
 from ..device import Device, DeviceType, get_cpu, get_device
 from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten, GroupNorm,
-                     Layer, LayerBuilder, LayerConfig, LayerFactory, MaxPool2D, ParameterizedLayer, ResidualBlock,
-                     create_layer, plan_fusion)
+                     GroupedConv2D, Layer, LayerBuilder, LayerConfig, LayerFactory, MaxPool2D, ParameterizedLayer,
+                     ResidualBlock, create_layer, plan_fusion)
 from .layers.base import run_backward
 from .params import ParamArena
 
@@ -674,6 +674,11 @@ class SequentialBuilder:
         return self._add(DepthwiseConv2D(self._shape[1], kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                          use_bias, self._n(name, "depthwise_conv2d")))
 
+    def grouped_conv2d(self, out_channels, kernel_h, kernel_w, groups, stride_h=1, stride_w=1, pad_h=0, pad_w=0,
+                       use_bias=True, name=""):
+        return self._add(GroupedConv2D(self._shape[1], out_channels, kernel_h, kernel_w, groups, stride_h, stride_w,
+                                       pad_h, pad_w, use_bias, self._n(name, "grouped_conv2d")))
+
     def dense(self, output_features, use_bias=True, name=""):
         feat = 1
         for d in self._shape[1:]:
@@ -732,6 +737,26 @@ class SequentialBuilder:
                 .batchnorm(1e-3, 0.1, True, "bn0")
                 .activation("relu")
                 .conv2d(mid_channels, 3, 3, stride, stride, 1, 1, False)
+                .batchnorm(1e-3, 0.1, True, "bn0")
+                .activation("relu")
+                .conv2d(out_channels, 1, 1, 1, 1, 0, 0, False)
+                .batchnorm(1e-3, 0.1, True, "bn0")
+                .build())
+        short = []
+        if stride != 1 or in_channels != out_channels:
+            short = (LayerBuilder().input(shape).conv2d(out_channels, 1, 1, stride, stride, 0, 0, False)
+                     .batchnorm(1e-3, 0.1, True, "bn0").build())
+        return self._add(ResidualBlock(main, short, "relu", name))
+
+    def resnext_bottleneck_block(self, in_channels, mid_channels, out_channels, groups, stride=1,
+                                 name="resnext_bottleneck_block"):
+        """:meth:`bottleneck_residual_block` with the 3x3 replaced by a grouped conv (Xie et al. 2017)."""
+        shape = [in_channels, self._shape[2], self._shape[3]]
+        main = (LayerBuilder().input(shape)
+                .conv2d(mid_channels, 1, 1, 1, 1, 0, 0, False)
+                .batchnorm(1e-3, 0.1, True, "bn0")
+                .activation("relu")
+                .grouped_conv2d(mid_channels, 3, 3, groups, stride, stride, 1, 1, False)
                 .batchnorm(1e-3, 0.1, True, "bn0")
                 .activation("relu")
                 .conv2d(out_channels, 1, 1, 1, 1, 0, 0, False)

@@ -242,6 +242,45 @@ def depthwise_conv2d_bwd(x, w, dy, stride, pad, grad_w, grad_b=None, need_dx=Tru
     return dx
 
 
+def _grouped_geom(what, x, w, groups, stride, pad):
+    N, Cc, H, W = x.shape
+    Co, Cig, KH, KW = w.shape
+    if groups < 1 or Cc % groups or Co % groups or Cig != Cc // groups:
+        raise ValueError(f"{what}: {Cc} input channels, weights {tuple(w.shape)}, groups {groups} (expected "
+                         f"({Co}, {Cc}/groups, KH, KW) with groups dividing both channel counts)")
+    OH, OW = _odim(H, KH, stride[0], pad[0]), _odim(W, KW, stride[1], pad[1])
+    if OH < 1 or OW < 1:
+        raise ValueError(f"{what}: kernel {KH}x{KW} does not fit the padded {H}x{W} input")
+    return N, Cc, H, W, Co, KH, KW, OH, OW
+
+
+def grouped_conv2d_fwd(x, w, bias, stride, pad, groups):
+    """Grouped conv (F.conv2d(groups=G)): w (Co,C/G,KH,KW), bias [Co] or None."""
+    x, w, bias = _c(x), _c(w), _c(bias)
+    _same(x, w, bias)
+    N, Cc, H, W, Co, KH, KW, OH, OW = _grouped_geom("grouped_conv2d", x, w, groups, stride, pad)
+    y = torch.empty((N, Co, OH, OW), dtype=x.dtype)
+    C().grouped_conv2d_fwd(dt(x), x.data_ptr(), w.data_ptr(), p(bias), y.data_ptr(), N, Cc, H, W, Co, groups, KH, KW,
+                           stride[0], stride[1], pad[0], pad[1])
+    return y
+
+
+def grouped_conv2d_bwd(x, w, dy, stride, pad, groups, grad_w, grad_b=None, need_dx=True):
+    """grad_w += dW, grad_b += sum(dy); returns dx (or None). grad_w/grad_b must be contiguous."""
+    x, w, dy = _c(x), _c(w), _c(dy)
+    _same(x, w, dy, grad_w, grad_b)
+    N, Cc, H, W, Co, KH, KW, OH, OW = _grouped_geom("grouped_conv2d_bwd", x, w, groups, stride, pad)
+    if tuple(dy.shape) != (N, Co, OH, OW):
+        raise ValueError(f"grouped_conv2d_bwd: x {tuple(x.shape)}, w {tuple(w.shape)}, dy {tuple(dy.shape)}")
+    for g in (grad_w, grad_b):
+        if g is not None and not g.is_contiguous():
+            raise ValueError("gradient accumulators must be contiguous")
+    dx = torch.empty_like(x) if need_dx else None
+    C().grouped_conv2d_bwd(dt(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), p(dx), grad_w.data_ptr(), p(grad_b), N,
+                           Cc, H, W, Co, groups, KH, KW, stride[0], stride[1], pad[0], pad[1])
+    return dx
+
+
 def dense_fwd(x2d, w2d, bias):
     x2d, w2d, bias = _c(x2d), _c(w2d), _c(bias)
     _same(x2d, w2d, bias)

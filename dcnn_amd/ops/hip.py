@@ -24,6 +24,7 @@ from .hip_convx import *  # noqa: F401,F403
 from .hip_convx import (conv2d_dgrad_im2col, conv2d_fwd_im2col, conv2d_wgrad_im2col, _im2col_ok,
                         stem_ok, stem_conv_fwd)
 from .hip_dw import *  # noqa: F401,F403  (depthwise conv: dwconv.hip)
+from .hip_gconv import *  # noqa: F401,F403  (grouped conv: gconv.hip)
 from .hip_layers import *  # noqa: F401,F403
 from .hip_layers import zero_
 from .hip_norm import *  # noqa: F401,F403
