@@ -114,18 +114,52 @@ class Layer {
   std::vector<Param> params_;
 };
 
-class Conv2D : public Layer {
+// What a 2-D convolution layer's geometry and parameters are, once for the three conv layers:
+// weights (Co, Ci / G, KH, KW) and an optional bias (Co), dense G == 1, depthwise Ci == Co == G.
+// forward / backward here are the depthwise and grouped passes (they differ in the gpu_ops /
+// cpu_ops entry only, chosen by depthwise()); Conv2D overrides both.
+class ConvBase : public Layer {
+ public:
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override;
+  Tensor backward(const Tensor& dy) override { return backward_impl(dy, nullptr); }
+  double flops(const std::vector<int64_t>& in) const override;
+  // GPU: backward whose input gradient also adds `residual` in the data-gradient epilogue (the
+  // shortcut gradient of a block whose main path starts with this layer), into dx; false: the
+  // layer has no such fusion (the caller runs backward and adds)
+  virtual bool backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
+    (void)dy; (void)residual; (void)dx;
+    return false;
+  }
+
+ protected:
+  ConvBase(int in_ch, int out_ch, int kh, int kw, int groups, int sh, int sw, int ph, int pw, bool bias,
+           std::string name)
+      : Layer(std::move(name)), ci_(in_ch), co_(out_ch), kh_(kh), kw_(kw), g_(groups), sh_(sh), sw_(sw), ph_(ph),
+        pw_(pw), bias_(bias) {}
+  ConvShape shape_for(const std::vector<int64_t>& in) const;
+  // stride_h .. use_bias into `p`, after the subclass's channel and kernel keys (the saved key order)
+  void geometry_config(json::Value& p) const;
+  const float* bias_value() const { return bias_ ? params_[1].value.ptr<float>() : nullptr; }
+  float* bias_grad() { return bias_ ? params_[1].grad.ptr<float>() : nullptr; }
+  // the dwconv kernels and their weight layout ([C][KH][KW] on every device): DepthwiseConv2D
+  virtual bool depthwise() const { return false; }
+  int group_in() const { return depthwise() ? 1 : ci_ / g_; }  // Ci / G
+  Tensor backward_impl(const Tensor& dy, const Tensor* residual);
+  int ci_, co_, kh_, kw_, g_, sh_, sw_, ph_, pw_;
+  bool bias_;
+};
+
+class Conv2D : public ConvBase {
  public:
   Conv2D(int in_ch, int out_ch, int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0, bool bias = true,
          std::string name = "conv2d");
   std::string type() const override { return "conv2d"; }
   json::Value parameters_config() const override;
-  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
-  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
   Tensor forward(const Tensor& x, bool training) override;
   Tensor backward(const Tensor& dy) override;
   bool takes_raw_input(const std::vector<int64_t>& in) const override;
-  double flops(const std::vector<int64_t>& in) const override;
   // GPU: hand the output's BatchNorm statistics, computed in the conv epilogue, to `bn` (the
   // BatchNorm that consumes this conv's output; fuse_bn_relu wires it)
   void set_stats_consumer(class BatchNorm* bn) { stats_to_ = bn; }
@@ -135,8 +169,7 @@ class Conv2D : public Layer {
   // the same across a residual-block boundary: the previous block's tail BatchNorm (its mask is
   // the block output), applied only by backward_residual (after the shortcut gradient is added)
   void set_block_bnb_producer(class BatchNorm* bn) { bnb_block_from_ = bn; }
-  // GPU: backward whose input gradient also adds `residual` in the data-gradient epilogue
-  Tensor backward_residual(const Tensor& dy, const Tensor& residual);
+  bool backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) override;
   // GPU RGB stem (the network input, fp32, on the stem kernel): true when this micro-batch's
   // forward ran it, so backward_stem_bn applies
   bool ran_stem() const;
@@ -149,9 +182,6 @@ class Conv2D : public Layer {
   bool make_transposed_operand(std::vector<int64_t>& row, long& tiles);
 
  private:
-  ConvShape shape_for(const std::vector<int64_t>& in) const;
-  int ci_, co_, kh_, kw_, sh_, sw_, ph_, pw_;
-  bool bias_;
   class BatchNorm* stats_to_ = nullptr;
   class BatchNorm* bnb_from_ = nullptr;
   class BatchNorm* bnb_block_from_ = nullptr;
@@ -159,49 +189,33 @@ class Conv2D : public Layer {
   const void* dgrad_operand(bool& transposed) const;
 };
 
-// Depthwise convolution (groups = C, channel multiplier 1): weights (C, 1, KH, KW). Not a Conv2D:
-// the fusion planner sees FK_OTHER (no statistics epilogue, no backward-BatchNorm fusion, no
-// transposed operand); the BatchNorm around it runs its own statistics passes.
-class DepthwiseConv2D : public Layer {
+// Depthwise convolution (groups = C, channel multiplier 1): weights (C, 1, KH, KW), NCHW and NHWC
+// the same bytes [C][KH][KW]. Shares ConvBase; not a Conv2D for the planner: it sees FK_OTHER (no
+// statistics epilogue, no backward-BatchNorm fusion, no transposed operand); the BatchNorm around
+// it runs its own statistics passes.
+class DepthwiseConv2D : public ConvBase {
  public:
   DepthwiseConv2D(int channels, int kh, int kw, int sh = 1, int sw = 1, int ph = 0, int pw = 0, bool bias = true,
                   std::string name = "depthwise_conv2d");
   std::string type() const override { return "depthwise_conv2d"; }
   json::Value parameters_config() const override;
-  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
-  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
-  Tensor forward(const Tensor& x, bool training) override;
-  Tensor backward(const Tensor& dy) override;
-  double flops(const std::vector<int64_t>& in) const override;
 
- private:
-  ConvShape shape_for(const std::vector<int64_t>& in) const;
-  int c_, kh_, kw_, sh_, sw_, ph_, pw_;
-  bool bias_;
+ protected:
+  bool depthwise() const override { return true; }
 };
 
-// Grouped convolution (1 < groups < channels): weights (Co, Ci / G, KH, KW). Not a Conv2D: the fusion
-// planner sees FK_OTHER (no statistics epilogue, no backward-BatchNorm fusion); the data gradient
-// can add a residual (the shortcut gradient of a block whose main path starts with it) in its store.
-class GroupedConv2D : public Layer {
+// Grouped convolution (1 < groups < channels): weights (Co, Ci / G, KH, KW). Shares ConvBase; not
+// a Conv2D for the planner: it sees FK_OTHER (no statistics epilogue, no backward-BatchNorm
+// fusion); the data gradient can add a residual (the shortcut gradient of a block whose main path
+// starts with it) in its store.
+class GroupedConv2D : public ConvBase {
  public:
   GroupedConv2D(int in_ch, int out_ch, int kh, int kw, int groups, int sh = 1, int sw = 1, int ph = 0, int pw = 0,
                 bool bias = true, std::string name = "grouped_conv2d");
   std::string type() const override { return "grouped_conv2d"; }
   json::Value parameters_config() const override;
-  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
-  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
-  Tensor forward(const Tensor& x, bool training) override;
-  Tensor backward(const Tensor& dy) override;
   // dx = conv^T(dy) + residual (GPU): wgrad + the fused data gradient
-  Tensor backward_residual(const Tensor& dy, const Tensor& residual);
-  double flops(const std::vector<int64_t>& in) const override;
-
- private:
-  ConvShape shape_for(const std::vector<int64_t>& in) const;
-  Tensor backward_impl(const Tensor& dy, const Tensor* residual);
-  int ci_, co_, kh_, kw_, g_, sh_, sw_, ph_, pw_;
-  bool bias_;
+  bool backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) override;
 };
 
 class Dense : public Layer {
@@ -524,6 +538,10 @@ class SequentialBuilder {
 
  private:
   std::string auto_name(const std::string& given, const std::string& kind);
+  // the conv builders' common ends: the running channel count (input() must have been called),
+  // and adding `l` with the running shape moved to its output
+  int conv_in() const;
+  SequentialBuilder& add_conv(std::unique_ptr<Layer> l);
   Sequential model_;
   std::vector<int64_t> cur_;  // current (C, H, W)
   int count_ = 0;

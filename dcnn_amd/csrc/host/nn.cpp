@@ -88,27 +88,16 @@ void Layer::sync_shadow() {
     if (p.shadow.defined()) gpu_ops::cast_bf16(p.value.ptr<float>(), p.shadow.data(), p.value.numel());
 }
 
-// ------------------------------------------------------------------ Conv2D
-Conv2D::Conv2D(int in_ch, int out_ch, int kh, int kw, int sh, int sw, int ph, int pw, bool bias, std::string name)
-    : Layer(std::move(name)), ci_(in_ch), co_(out_ch), kh_(kh), kw_(kw), sh_(sh), sw_(sw), ph_(ph), pw_(pw),
-      bias_(bias) {}
-
-json::Value Conv2D::parameters_config() const {
-  json::Value p = json::Value::object();
-  p["in_channels"] = ci_;
-  p["out_channels"] = co_;
-  p["kernel_h"] = kh_;
-  p["kernel_w"] = kw_;
+// ------------------------------------------------------------------ ConvBase
+void ConvBase::geometry_config(json::Value& p) const {
   p["stride_h"] = sh_;
   p["stride_w"] = sw_;
   p["pad_h"] = ph_;
   p["pad_w"] = pw_;
   p["use_bias"] = bias_;
-  p["optimized"] = "mfma";
-  return p;
 }
 
-ConvShape Conv2D::shape_for(const std::vector<int64_t>& in) const {
+ConvShape ConvBase::shape_for(const std::vector<int64_t>& in) const {
   ConvShape s{};
   s.N = (int)in[0];
   s.C = (int)in[1];
@@ -128,26 +117,96 @@ ConvShape Conv2D::shape_for(const std::vector<int64_t>& in) const {
   return s;
 }
 
-std::vector<int64_t> Conv2D::output_shape(const std::vector<int64_t>& in) const {
+std::vector<int64_t> ConvBase::output_shape(const std::vector<int64_t>& in) const {
   const ConvShape s = shape_for(in);
   return {in[0], co_, s.OH, s.OW};
 }
 
-void Conv2D::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+void ConvBase::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
   (void)in;
   dev_ = dev;
   params_.clear();
-  const float bound = 1.f / std::sqrt((float)(ci_ * kh_ * kw_));
-  // GPU: physical [Co][KH][KW][Ci] (the GEMM B operand); CPU: NCHW
-  const Layout wl = dev.is_gpu() ? Layout::NHWC : Layout::NCHW;
-  add_param("weights", {co_, ci_, kh_, kw_}, wl, uniform_init((size_t)co_ * ci_ * kh_ * kw_, bound, seed));
+  const int cig = group_in();
+  const float bound = 1.f / std::sqrt((float)(cig * kh_ * kw_));  // one group's fan-in
+  // GPU: physical [Co][KH][KW][Ci / G] (the GEMM / MFMA B operand); CPU: NCHW. Depthwise
+  // (C, 1, KH, KW): NCHW and NHWC are the same bytes [C][KH][KW]
+  const Layout wl = dev.is_gpu() && !depthwise() ? Layout::NHWC : Layout::NCHW;
+  add_param("weights", {co_, cig, kh_, kw_}, wl, uniform_init((size_t)co_ * cig * kh_ * kw_, bound, seed));
   if (bias_) add_param("bias", {co_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)co_, bound, seed + 1));
 }
 
-double Conv2D::flops(const std::vector<int64_t>& in) const {
+double ConvBase::flops(const std::vector<int64_t>& in) const {
   const ConvShape s = shape_for(in);
-  const double out = (double)s.N * s.OH * s.OW, k = (double)ci_ * kh_ * kw_;
+  const double out = (double)s.N * s.OH * s.OW, k = (double)group_in() * kh_ * kw_;  // a dense conv's / G
   return 6.0 * co_ * k * out + (bias_ ? 2.0 * co_ * out : 0.0);  // forward 2, backward 4 per MAC
+}
+
+Tensor ConvBase::forward(const Tensor& x, bool training) {
+  (void)training;
+  check_act(x, dev_, type().c_str());
+  const ConvShape s = shape_for(x.shape());
+  Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
+  const float* b = bias_value();
+  if (dev_.is_gpu()) {
+    const void* w = params_[0].shadow.data();
+    if (depthwise())
+      gpu_ops::dwconv_fwd(x.data(), w, b, y.data(), s);
+    else
+      gpu_ops::gconv_fwd(x.data(), w, b, y.data(), s, g_);
+  } else {
+    const float* w = params_[0].value.ptr<float>();
+    if (depthwise())
+      cpu_ops::dwconv_fwd(x.ptr<float>(), w, b, y.ptr<float>(), s);
+    else
+      cpu_ops::gconv_fwd(x.ptr<float>(), w, b, y.ptr<float>(), s, g_);
+  }
+  mbc().a = x;
+  return y;
+}
+
+Tensor ConvBase::backward_impl(const Tensor& dy, const Tensor* residual) {
+  const Tensor& x_ = mbc().a;
+  const ConvShape s = shape_for(x_.shape());
+  float* gw = params_[0].grad.ptr<float>();
+  float* gb = bias_grad();
+  if (dev_.is_gpu()) {
+    if (depthwise())
+      gpu_ops::dwconv_wgrad(dy.data(), x_.data(), gw, gb, s);
+    else
+      gpu_ops::gconv_wgrad(dy.data(), x_.data(), gw, gb, s, g_);
+    if (!input_grad_ && residual == nullptr) return Tensor();
+    Tensor dx = act_empty(x_.shape(), dev_);
+    const void* w = params_[0].shadow.data();
+    const void* r = residual ? residual->data() : nullptr;
+    if (depthwise())
+      gpu_ops::dwconv_dgrad(dy.data(), w, dx.data(), s, r);
+    else
+      gpu_ops::gconv_dgrad(dy.data(), w, dx.data(), s, g_, r);
+    return dx;
+  }
+  Tensor dx = input_grad_ ? act_empty(x_.shape(), dev_) : Tensor();
+  float* dxp = input_grad_ ? dx.ptr<float>() : nullptr;
+  const float* w = params_[0].value.ptr<float>();
+  if (depthwise())
+    cpu_ops::dwconv_bwd(x_.ptr<float>(), w, dy.ptr<float>(), dxp, gw, gb, s);
+  else
+    cpu_ops::gconv_bwd(x_.ptr<float>(), w, dy.ptr<float>(), dxp, gw, gb, s, g_);
+  return dx;
+}
+
+// ------------------------------------------------------------------ Conv2D
+Conv2D::Conv2D(int in_ch, int out_ch, int kh, int kw, int sh, int sw, int ph, int pw, bool bias, std::string name)
+    : ConvBase(in_ch, out_ch, kh, kw, 1, sh, sw, ph, pw, bias, std::move(name)) {}
+
+json::Value Conv2D::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["in_channels"] = ci_;
+  p["out_channels"] = co_;
+  p["kernel_h"] = kh_;
+  p["kernel_w"] = kw_;
+  geometry_config(p);
+  p["optimized"] = "mfma";
+  return p;
 }
 
 bool Conv2D::takes_raw_input(const std::vector<int64_t>& in) const {
@@ -159,7 +218,7 @@ Tensor Conv2D::forward(const Tensor& x, bool training) {
   check_act(x, dev_, "conv2d");
   const ConvShape s = shape_for(x.shape());
   Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
-  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
+  const float* b = bias_value();
   if (dev_.is_gpu() && x.dtype() == DType::F32) {
     // the network input, fp32 NCHW, on the RGB stem kernel (Sequential::input_activation)
     if (x.layout() != Layout::NCHW || !gpu_ops::stem_ok(s)) throw std::runtime_error(name_ + ": fp32 input");
@@ -189,14 +248,13 @@ bool Conv2D::ran_stem() const {
 void Conv2D::backward_stem_bn(const Tensor& dy, const gpu_ops::StemBn& bn) {
   const Tensor& x_ = mbc().a;
   const ConvShape s = shape_for(x_.shape());
-  gpu_ops::stem_wgrad_bn(dy.data(), x_.ptr<float>(), params_[0].grad.ptr<float>(),
-                         bias_ ? params_[1].grad.ptr<float>() : nullptr, s, bn);
+  gpu_ops::stem_wgrad_bn(dy.data(), x_.ptr<float>(), params_[0].grad.ptr<float>(), bias_grad(), s, bn);
 }
 
 Tensor Conv2D::backward(const Tensor& dy) {
   const Tensor& x_ = mbc().a;
   const ConvShape s = shape_for(x_.shape());
-  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
+  float* gb = bias_grad();
   if (dev_.is_gpu() && x_.dtype() == DType::F32) {  // stem: the input needs no gradient
     gpu_ops::stem_wgrad(dy.data(), x_.ptr<float>(), params_[0].grad.ptr<float>(), gb, s);
     return Tensor();
@@ -225,14 +283,14 @@ Tensor Conv2D::backward(const Tensor& dy) {
   return dx;
 }
 
-Tensor Conv2D::backward_residual(const Tensor& dy, const Tensor& residual) {
+bool Conv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
   const Tensor& x_ = mbc().a;
   if (!dev_.is_gpu() || x_.dtype() == DType::F32 || residual.shape() != x_.shape())
     throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
   const ConvShape s = shape_for(x_.shape());
-  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
+  float* gb = bias_grad();
   gpu_ops::conv_wgrad(dy.data(), x_.data(), params_[0].grad.ptr<float>(), gb, s);
-  Tensor dx = act_empty(x_.shape(), dev_);
+  dx = act_empty(x_.shape(), dev_);
   bool tr = false;
   const void* w = dgrad_operand(tr);
   if (bnb_block_from_ != nullptr) {
@@ -240,108 +298,30 @@ Tensor Conv2D::backward_residual(const Tensor& dy, const Tensor& residual) {
     int rows = 0;
     const float* st = gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr, &ops, &rows);
     if (rows > 0) bnb_block_from_->offer_bwd_stats(dx.data(), st, rows);
-    return dx;
+    return true;
   }
   gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr);
-  return dx;
+  return true;
 }
 
 // ------------------------------------------------------------------ DepthwiseConv2D
 DepthwiseConv2D::DepthwiseConv2D(int channels, int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
                                  std::string name)
-    : Layer(std::move(name)), c_(channels), kh_(kh), kw_(kw), sh_(sh), sw_(sw), ph_(ph), pw_(pw), bias_(bias) {}
+    : ConvBase(channels, channels, kh, kw, channels, sh, sw, ph, pw, bias, std::move(name)) {}
 
 json::Value DepthwiseConv2D::parameters_config() const {
   json::Value p = json::Value::object();
-  p["channels"] = c_;
+  p["channels"] = ci_;
   p["kernel_h"] = kh_;
   p["kernel_w"] = kw_;
-  p["stride_h"] = sh_;
-  p["stride_w"] = sw_;
-  p["pad_h"] = ph_;
-  p["pad_w"] = pw_;
-  p["use_bias"] = bias_;
+  geometry_config(p);
   return p;
-}
-
-ConvShape DepthwiseConv2D::shape_for(const std::vector<int64_t>& in) const {
-  ConvShape s{};
-  s.N = (int)in[0];
-  s.C = (int)in[1];
-  s.H = (int)in[2];
-  s.W = (int)in[3];
-  s.Co = c_;
-  s.KH = kh_;
-  s.KW = kw_;
-  s.SH = sh_;
-  s.SW = sw_;
-  s.PH = ph_;
-  s.PW = pw_;
-  s.OH = (s.H + 2 * ph_ - kh_) / sh_ + 1;
-  s.OW = (s.W + 2 * pw_ - kw_) / sw_ + 1;
-  if (s.C != c_) throw std::runtime_error(name_ + ": input has " + std::to_string(s.C) + " channels, expected " +
-                                          std::to_string(c_));
-  return s;
-}
-
-std::vector<int64_t> DepthwiseConv2D::output_shape(const std::vector<int64_t>& in) const {
-  const ConvShape s = shape_for(in);
-  return {in[0], c_, s.OH, s.OW};
-}
-
-void DepthwiseConv2D::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
-  (void)in;
-  dev_ = dev;
-  params_.clear();
-  const float bound = 1.f / std::sqrt((float)(kh_ * kw_));  // Conv2D's rule, one input channel per group
-  // (C, 1, KH, KW): NCHW and NHWC are the same bytes [C][KH][KW]
-  add_param("weights", {c_, 1, kh_, kw_}, Layout::NCHW, uniform_init((size_t)c_ * kh_ * kw_, bound, seed));
-  if (bias_) add_param("bias", {c_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)c_, bound, seed + 1));
-}
-
-double DepthwiseConv2D::flops(const std::vector<int64_t>& in) const {
-  const ConvShape s = shape_for(in);
-  const double out = (double)s.N * s.OH * s.OW;
-  return 6.0 * c_ * kh_ * kw_ * out + (bias_ ? 2.0 * c_ * out : 0.0);  // forward 2, backward 4 per MAC
-}
-
-Tensor DepthwiseConv2D::forward(const Tensor& x, bool training) {
-  (void)training;
-  check_act(x, dev_, "depthwise_conv2d");
-  const ConvShape s = shape_for(x.shape());
-  Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
-  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
-  if (dev_.is_gpu())
-    gpu_ops::dwconv_fwd(x.data(), params_[0].shadow.data(), b, y.data(), s);
-  else
-    cpu_ops::dwconv_fwd(x.ptr<float>(), params_[0].value.ptr<float>(), b, y.ptr<float>(), s);
-  mbc().a = x;
-  return y;
-}
-
-Tensor DepthwiseConv2D::backward(const Tensor& dy) {
-  const Tensor& x_ = mbc().a;
-  const ConvShape s = shape_for(x_.shape());
-  float* gw = params_[0].grad.ptr<float>();
-  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
-  if (dev_.is_gpu()) {
-    gpu_ops::dwconv_wgrad(dy.data(), x_.data(), gw, gb, s);
-    if (!input_grad_) return Tensor();
-    Tensor dx = act_empty(x_.shape(), dev_);
-    gpu_ops::dwconv_dgrad(dy.data(), params_[0].shadow.data(), dx.data(), s);
-    return dx;
-  }
-  Tensor dx = input_grad_ ? act_empty(x_.shape(), dev_) : Tensor();
-  cpu_ops::dwconv_bwd(x_.ptr<float>(), params_[0].value.ptr<float>(), dy.ptr<float>(),
-                      input_grad_ ? dx.ptr<float>() : nullptr, gw, gb, s);
-  return dx;
 }
 
 // ------------------------------------------------------------------ GroupedConv2D
 GroupedConv2D::GroupedConv2D(int in_ch, int out_ch, int kh, int kw, int groups, int sh, int sw, int ph, int pw,
                              bool bias, std::string name)
-    : Layer(std::move(name)), ci_(in_ch), co_(out_ch), kh_(kh), kw_(kw), g_(groups), sh_(sh), sw_(sw), ph_(ph),
-      pw_(pw), bias_(bias) {
+    : ConvBase(in_ch, out_ch, kh, kw, groups, sh, sw, ph, pw, bias, std::move(name)) {
   if (g_ == 1) throw std::invalid_argument(name_ + ": groups == 1, use Conv2D");
   if (g_ == ci_ && g_ == co_)
     throw std::invalid_argument(name_ + ": groups == in == out channels, use DepthwiseConv2D");
@@ -357,95 +337,15 @@ json::Value GroupedConv2D::parameters_config() const {
   p["kernel_h"] = kh_;
   p["kernel_w"] = kw_;
   p["groups"] = g_;
-  p["stride_h"] = sh_;
-  p["stride_w"] = sw_;
-  p["pad_h"] = ph_;
-  p["pad_w"] = pw_;
-  p["use_bias"] = bias_;
+  geometry_config(p);
   return p;
 }
 
-ConvShape GroupedConv2D::shape_for(const std::vector<int64_t>& in) const {
-  ConvShape s{};
-  s.N = (int)in[0];
-  s.C = (int)in[1];
-  s.H = (int)in[2];
-  s.W = (int)in[3];
-  s.Co = co_;
-  s.KH = kh_;
-  s.KW = kw_;
-  s.SH = sh_;
-  s.SW = sw_;
-  s.PH = ph_;
-  s.PW = pw_;
-  s.OH = (s.H + 2 * ph_ - kh_) / sh_ + 1;
-  s.OW = (s.W + 2 * pw_ - kw_) / sw_ + 1;
-  if (s.C != ci_) throw std::runtime_error(name_ + ": input has " + std::to_string(s.C) + " channels, expected " +
-                                           std::to_string(ci_));
-  return s;
-}
-
-std::vector<int64_t> GroupedConv2D::output_shape(const std::vector<int64_t>& in) const {
-  const ConvShape s = shape_for(in);
-  return {in[0], co_, s.OH, s.OW};
-}
-
-void GroupedConv2D::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
-  (void)in;
-  dev_ = dev;
-  params_.clear();
-  const int cig = ci_ / g_;
-  const float bound = 1.f / std::sqrt((float)(cig * kh_ * kw_));  // Conv2D's rule, one group's fan-in
-  // GPU: physical [Co][KH][KW][Ci / G] (the MFMA operand); CPU: NCHW
-  const Layout wl = dev.is_gpu() ? Layout::NHWC : Layout::NCHW;
-  add_param("weights", {co_, cig, kh_, kw_}, wl, uniform_init((size_t)co_ * cig * kh_ * kw_, bound, seed));
-  if (bias_) add_param("bias", {co_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)co_, bound, seed + 1));
-}
-
-double GroupedConv2D::flops(const std::vector<int64_t>& in) const {
-  const ConvShape s = shape_for(in);
-  const double out = (double)s.N * s.OH * s.OW, k = (double)(ci_ / g_) * kh_ * kw_;  // a dense conv's / G
-  return 6.0 * co_ * k * out + (bias_ ? 2.0 * co_ * out : 0.0);  // forward 2, backward 4 per MAC
-}
-
-Tensor GroupedConv2D::forward(const Tensor& x, bool training) {
-  (void)training;
-  check_act(x, dev_, "grouped_conv2d");
-  const ConvShape s = shape_for(x.shape());
-  Tensor y = act_empty({s.N, s.Co, s.OH, s.OW}, dev_);
-  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
-  if (dev_.is_gpu())
-    gpu_ops::gconv_fwd(x.data(), params_[0].shadow.data(), b, y.data(), s, g_);
-  else
-    cpu_ops::gconv_fwd(x.ptr<float>(), params_[0].value.ptr<float>(), b, y.ptr<float>(), s, g_);
-  mbc().a = x;
-  return y;
-}
-
-Tensor GroupedConv2D::backward_impl(const Tensor& dy, const Tensor* residual) {
-  const Tensor& x_ = mbc().a;
-  const ConvShape s = shape_for(x_.shape());
-  float* gw = params_[0].grad.ptr<float>();
-  float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
-  if (dev_.is_gpu()) {
-    gpu_ops::gconv_wgrad(dy.data(), x_.data(), gw, gb, s, g_);
-    if (!input_grad_ && residual == nullptr) return Tensor();
-    Tensor dx = act_empty(x_.shape(), dev_);
-    gpu_ops::gconv_dgrad(dy.data(), params_[0].shadow.data(), dx.data(), s, g_, residual ? residual->data() : nullptr);
-    return dx;
-  }
-  Tensor dx = input_grad_ ? act_empty(x_.shape(), dev_) : Tensor();
-  cpu_ops::gconv_bwd(x_.ptr<float>(), params_[0].value.ptr<float>(), dy.ptr<float>(),
-                     input_grad_ ? dx.ptr<float>() : nullptr, gw, gb, s, g_);
-  return dx;
-}
-
-Tensor GroupedConv2D::backward(const Tensor& dy) { return backward_impl(dy, nullptr); }
-
-Tensor GroupedConv2D::backward_residual(const Tensor& dy, const Tensor& residual) {
+bool GroupedConv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
   if (!dev_.is_gpu() || residual.shape() != mbc().a.shape())
     throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
-  return backward_impl(dy, &residual);
+  dx = backward_impl(dy, &residual);
+  return true;
 }
 
 gpu_ops::BnbOperands BatchNorm::bnb_operands(int mb) {
@@ -1201,14 +1101,15 @@ Tensor ResidualBlock::backward(const Tensor& dy) {
     }
     for (size_t i = main_.size() - 1; i-- > 1;) gm = main_[i]->backward(gm);
     // the main path's first conv adds the shortcut gradient in its data-gradient epilogue
-    auto* head = dynamic_cast<Conv2D*>(main_[0].get());
-    if (head != nullptr && input_grad_ && gs.defined() && gs.dtype() == DType::BF16) return head->backward_residual(gm, gs);
-    auto* ghead = dynamic_cast<GroupedConv2D*>(main_[0].get());
-    if (ghead != nullptr && main_.size() > 1 && input_grad_ && gs.defined() && gs.dtype() == DType::BF16)
-      return ghead->backward_residual(gm, gs);
+    // (the dense and grouped layers; the fused tail is main_.back(), so main_[0] is not the tail)
+    auto* head = dynamic_cast<ConvBase*>(main_[0].get());
+    Tensor dx;
+    if (head != nullptr && input_grad_ && gs.defined() && gs.dtype() == DType::BF16 &&
+        head->backward_residual(gm, gs, dx))
+      return dx;
     gm = main_[0]->backward(gm);
     if (!gm.defined() || !gs.defined()) return Tensor();
-    Tensor dx = act_empty(gm.shape(), dev_);
+    dx = act_empty(gm.shape(), dev_);
     gpu_ops::add(gm.data(), gs.data(), dx.data(), dx.numel(), false);
     return dx;
   }
@@ -1768,36 +1669,36 @@ SequentialBuilder& SequentialBuilder::input(const std::vector<int64_t>& chw) {
   return *this;
 }
 
-SequentialBuilder& SequentialBuilder::conv2d(int out_ch, int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
-                                             const std::string& name) {
+int SequentialBuilder::conv_in() const {
   if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
-  auto l = std::make_unique<Conv2D>((int)cur_[0], out_ch, kh, kw, sh, sw, ph, pw, bias, auto_name(name, "conv2d"));
+  return (int)cur_[0];
+}
+
+SequentialBuilder& SequentialBuilder::add_conv(std::unique_ptr<Layer> l) {
   const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
   cur_ = {o[1], o[2], o[3]};
   model_.add(std::move(l));
   return *this;
+}
+
+SequentialBuilder& SequentialBuilder::conv2d(int out_ch, int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
+                                             const std::string& name) {
+  const int ci = conv_in();
+  return add_conv(std::make_unique<Conv2D>(ci, out_ch, kh, kw, sh, sw, ph, pw, bias, auto_name(name, "conv2d")));
 }
 
 SequentialBuilder& SequentialBuilder::depthwise_conv2d(int kh, int kw, int sh, int sw, int ph, int pw, bool bias,
                                                        const std::string& name) {
-  if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
-  auto l = std::make_unique<DepthwiseConv2D>((int)cur_[0], kh, kw, sh, sw, ph, pw, bias,
-                                             auto_name(name, "depthwise_conv2d"));
-  const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
-  cur_ = {o[1], o[2], o[3]};
-  model_.add(std::move(l));
-  return *this;
+  const int c = conv_in();
+  return add_conv(
+      std::make_unique<DepthwiseConv2D>(c, kh, kw, sh, sw, ph, pw, bias, auto_name(name, "depthwise_conv2d")));
 }
 
 SequentialBuilder& SequentialBuilder::grouped_conv2d(int out_ch, int kh, int kw, int groups, int sh, int sw, int ph,
                                                      int pw, bool bias, const std::string& name) {
-  if (cur_.empty()) throw std::logic_error("SequentialBuilder: call input() first");
-  auto l = std::make_unique<GroupedConv2D>((int)cur_[0], out_ch, kh, kw, groups, sh, sw, ph, pw, bias,
-                                           auto_name(name, "grouped_conv2d"));
-  const auto o = l->output_shape({1, cur_[0], cur_[1], cur_[2]});
-  cur_ = {o[1], o[2], o[3]};
-  model_.add(std::move(l));
-  return *this;
+  const int ci = conv_in();
+  return add_conv(std::make_unique<GroupedConv2D>(ci, out_ch, kh, kw, groups, sh, sw, ph, pw, bias,
+                                                  auto_name(name, "grouped_conv2d")));
 }
 
 SequentialBuilder& SequentialBuilder::batchnorm(float eps, float momentum, bool affine, const std::string& name) {

@@ -535,6 +535,17 @@ void wgrad_reduce(const Tensor& hold, const Tensor& bhold, const float* slab, fl
   else
     splitk_reduce(slab, gw, n, splits, 1, cur());
 }
+
+// one split weight gradient: `splits` partial slabs of n weight and (with gb) nb bias elements,
+// written by launch(slab, bslab), then summed in fixed order into gw / gb (+=)
+template <class Launch>
+void wgrad_split(int splits, long n, long nb, float* gw, float* gb, Launch&& launch) {
+  Tensor hold, bhold;
+  float* slab = wgrad_slab(SLAB, (size_t)splits * n * 4, hold);
+  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * nb * 4, bhold) : nullptr;
+  launch(slab, bslab);
+  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, nb, splits);
+}
 }  // namespace
 
 void begin_deferred_reduce() { g_defer = true; }
@@ -758,59 +769,52 @@ void conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvS
   const long dyb = (long)P * s.Co * 2, xb = (long)s.N * s.H * s.W * s.C * 2;
   const int route = conv_wgrad_route(route_geom(s, -1));  // shared routing table (conv_route.cpp)
   rec("wgrad", s, route, {{"bias", gb != nullptr}, {"deferred", g_defer}});
+  const long n = (long)s.Co * Ng;
   if (route == ROUTE_HALO) {
     const int splits = hwgrad_splits(s.N, s.H, s.W, s.C, s.Co);
-    Tensor hold, bhold;
-    float* slab = wgrad_slab(SLAB, (size_t)splits * s.Co * Ng * 4, hold);
-    float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
-    HWArgs a{};
-    a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-    a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
-    a.NB = s.N; a.H = s.H; a.W = s.W; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
-    for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3 - 1; a.tap_dx[t] = t % 3 - 1; }
-    hwgrad(a, splits, cur());
-    wgrad_reduce(hold, bhold, slab, gw, (long)s.Co * Ng, bslab, gb, s.Co, splits);
+    wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
+      HWArgs a{};
+      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
+      a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
+      a.NB = s.N; a.H = s.H; a.W = s.W; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
+      for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3 - 1; a.tap_dx[t] = t % 3 - 1; }
+      hwgrad(a, splits, cur());
+    });
     return;
   }
   if (route == ROUTE_HALO_S2) {  // 3x3 stride 2: the stride-2 halo kernel (dY grid OH x OW)
     const int splits = hwgrad_s2_splits(s.N, s.OH, s.OW, s.C, s.Co);
-    Tensor hold, bhold;
-    float* slab = wgrad_slab(SLAB, (size_t)splits * s.Co * Ng * 4, hold);
-    float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
-    HWArgs a{};
-    a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-    a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
-    a.NB = s.N; a.H = s.OH; a.W = s.OW; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
-    hwgrad_s2(a, splits, cur());
-    wgrad_reduce(hold, bhold, slab, gw, (long)s.Co * Ng, bslab, gb, s.Co, splits);
+    wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
+      HWArgs a{};
+      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
+      a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
+      a.NB = s.N; a.H = s.OH; a.W = s.OW; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
+      hwgrad_s2(a, splits, cur());
+    });
     return;
   }
-  if ((route == ROUTE_GEMM_G2 || route == ROUTE_HALO_S2) && dyb < (1l << 31) && xb < (1l << 31) && P < (1 << 24)) {
+  if (route == ROUTE_GEMM_G2 && dyb < (1l << 31) && xb < (1l << 31) && P < (1 << 24)) {
     const int splits = gemm_t2_splits(s.Co, Ng, P);
-    Tensor hold, bhold;
-    float* slab = wgrad_slab(SLAB, (size_t)splits * s.Co * Ng * 4, hold);
-    float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
-    T2Args a{};
-    a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-    a.a_bytes = (unsigned)dyb; a.b_bytes = (unsigned)xb;
-    a.M = s.Co; a.N = Ng; a.P = P; a.ldy = s.Co; a.Cs = s.C; a.H = s.H; a.W = s.W; a.GH = s.OH; a.GW = s.OW;
-    a.SY = s.SH; a.SX = s.SW;
-    int t = 0;
-    for (int ky = 0; ky < s.KH; ++ky)
-      for (int kx = 0; kx < s.KW; ++kx, ++t) { a.tap_dy[t] = ky - s.PH; a.tap_dx[t] = kx - s.PW; }
-    a.ntaps = t;
-    gemm_t2(a, splits, cur());
-    wgrad_reduce(hold, bhold, slab, gw, (long)s.Co * Ng, bslab, gb, s.Co, splits);
+    wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
+      T2Args a{};
+      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
+      a.a_bytes = (unsigned)dyb; a.b_bytes = (unsigned)xb;
+      a.M = s.Co; a.N = Ng; a.P = P; a.ldy = s.Co; a.Cs = s.C; a.H = s.H; a.W = s.W; a.GH = s.OH; a.GW = s.OW;
+      a.SY = s.SH; a.SX = s.SW;
+      int t = 0;
+      for (int ky = 0; ky < s.KH; ++ky)
+        for (int kx = 0; kx < s.KW; ++kx, ++t) { a.tap_dy[t] = ky - s.PH; a.tap_dx[t] = kx - s.PW; }
+      a.ntaps = t;
+      gemm_t2(a, splits, cur());
+    });
     return;
   }
   const int splits = gemm_tn_splits(s.Co, Ng, P);
-  Tensor hold, bhold;
-  float* slab = wgrad_slab(SLAB, (size_t)splits * s.Co * Ng * 4, hold);
-  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
-  TnArgs a{static_cast<const bf16*>(dy), static_cast<const bf16*>(x), slab, bslab, s.Co, Ng, P, kConvFwd, s.N, s.H,
-           s.W, s.C, s.OH, s.OW, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW, 0, 0};
-  gemm_tn(a, splits, cur());
-  wgrad_reduce(hold, bhold, slab, gw, (long)s.Co * Ng, bslab, gb, s.Co, splits);
+  wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
+    TnArgs a{static_cast<const bf16*>(dy), static_cast<const bf16*>(x), slab, bslab, s.Co, Ng, P, kConvFwd, s.N, s.H,
+             s.W, s.C, s.OH, s.OW, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW, 0, 0};
+    gemm_tn(a, splits, cur());
+  });
 }
 
 // ---- depthwise conv (dwconv.hip): streaming kernels outside the routing table (route -1)
@@ -835,12 +839,8 @@ void dwconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const Con
   rec("dw_wgrad", s, -1, {{"bias", gb != nullptr}, {"deferred", g_defer}});
   const DwArgs g = dw_args(s, "dwconv_wgrad");
   const int splits = dcnn::dwconv_wgrad_splits(kBF16, g);
-  const long n = (long)s.C * s.KH * s.KW;
-  Tensor hold, bhold;
-  float* slab = wgrad_slab(SLAB, (size_t)splits * n * 4, hold);
-  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.C * 4, bhold) : nullptr;
-  dcnn::dwconv_wgrad(kBF16, dy, x, slab, bslab, g, cur());
-  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.C, splits);
+  wgrad_split(splits, (long)s.C * s.KH * s.KW, s.C, gw, gb,
+              [&](float* slab, float* bslab) { dcnn::dwconv_wgrad(kBF16, dy, x, slab, bslab, g, cur()); });
 }
 
 // ---- grouped conv (gconv.hip): MFMA kernels outside the routing table (route -1)
@@ -868,12 +868,8 @@ void gconv_wgrad(const void* dy, const void* x, float* gw, float* gb, const Conv
   rec("gc_wgrad", s, -1, {{"bias", gb != nullptr}, {"deferred", g_defer}});
   const GcArgs g = gc_args(s, groups);
   const int splits = dcnn::gconv_wgrad_splits(kBF16, g);
-  const long n = (long)s.Co * s.KH * s.KW * (s.C / groups);
-  Tensor hold, bhold;
-  float* slab = wgrad_slab(SLAB, (size_t)splits * n * 4, hold);
-  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * s.Co * 4, bhold) : nullptr;
-  dcnn::gconv_wgrad(kBF16, dy, x, slab, bslab, g, cur());
-  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.Co, splits);
+  wgrad_split(splits, (long)s.Co * s.KH * s.KW * (s.C / groups), s.Co, gw, gb,
+              [&](float* slab, float* bslab) { dcnn::gconv_wgrad(kBF16, dy, x, slab, bslab, g, cur()); });
 }
 
 bool stem_ok(const ConvShape& s) {
@@ -917,21 +913,19 @@ static void stem_wgrad_impl(const void* dy, const float* x, float* gw, float* gb
   if (bn) st = reduce_stats(1, bn->slab, bn->rows, s.Co);  // (before the slab scratch below is taken)
   const int blocks = bn ? stem_wgrad_blocks_bnt(s.N, s.H, s.W) : stem_wgrad_blocks(s.N, s.H, s.W);
   const long n = 9l * s.C * s.Co;
-  Tensor hold, bhold;
-  float* slab = wgrad_slab(SLAB, (size_t)blocks * n * 4, hold);
-  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)blocks * s.Co * 4, bhold) : nullptr;
-  StemArgs a{};
-  a.x = x; a.dy = static_cast<const bf16*>(dy); a.slab = slab; a.bias_slab = bslab;
-  a.gs[0] = 9l * s.C; a.gs[1] = 1; a.gs[2] = 3l * s.C; a.gs[3] = s.C;
-  a.n_slab = n;
-  a.N = s.N; a.Ci = s.C; a.H = s.H; a.W = s.W; a.Co = s.Co;
-  if (bn) {
-    a.bn_x = static_cast<const bf16*>(bn->x); a.bn_mean = bn->mean; a.bn_istd = bn->istd; a.bn_gamma = bn->gamma;
-    a.bn_sums = st.first; a.bn_parts = st.second; a.bn_count = (float)((long)s.N * s.H * s.W);
-    a.bn_dgamma = bn->dgamma; a.bn_dbeta = bn->dbeta; a.bn_eval = bn->train ? 0 : 1;
-  }
-  dcnn::stem_wgrad(a, blocks, cur());
-  wgrad_reduce(hold, bhold, slab, gw, n, bslab, gb, s.Co, blocks);
+  wgrad_split(blocks, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
+    StemArgs a{};
+    a.x = x; a.dy = static_cast<const bf16*>(dy); a.slab = slab; a.bias_slab = bslab;
+    a.gs[0] = 9l * s.C; a.gs[1] = 1; a.gs[2] = 3l * s.C; a.gs[3] = s.C;
+    a.n_slab = n;
+    a.N = s.N; a.Ci = s.C; a.H = s.H; a.W = s.W; a.Co = s.Co;
+    if (bn) {
+      a.bn_x = static_cast<const bf16*>(bn->x); a.bn_mean = bn->mean; a.bn_istd = bn->istd; a.bn_gamma = bn->gamma;
+      a.bn_sums = st.first; a.bn_parts = st.second; a.bn_count = (float)((long)s.N * s.H * s.W);
+      a.bn_dgamma = bn->dgamma; a.bn_dbeta = bn->dbeta; a.bn_eval = bn->train ? 0 : 1;
+    }
+    dcnn::stem_wgrad(a, blocks, cur());
+  });
 }
 
 void dense_fwd(const void* x, const void* w, const float* bias, void* y, int N, int In, int Out) {
@@ -950,13 +944,11 @@ void dense_dgrad(const void* dy, const void* w, void* dx, int N, int In, int Out
 
 void dense_wgrad(const void* dy, const void* x, float* gw, float* gb, int N, int In, int Out) {
   const int splits = gemm_tn_splits(Out, In, N);
-  Tensor hold, bhold;
-  float* slab = wgrad_slab(SLAB, (size_t)splits * Out * In * 4, hold);
-  float* bslab = gb ? wgrad_slab(BSLAB, (size_t)splits * Out * 4, bhold) : nullptr;
-  TnArgs a{static_cast<const bf16*>(dy), static_cast<const bf16*>(x), slab, bslab, Out, In, N, kPlain, 0, 0, 0, 0, 1,
-           1, 1, 1, 1, 1, 0, 0, In, 0};
-  gemm_tn(a, splits, cur());
-  wgrad_reduce(hold, bhold, slab, gw, (long)Out * In, bslab, gb, Out, splits);
+  wgrad_split(splits, (long)Out * In, Out, gw, gb, [&](float* slab, float* bslab) {
+    TnArgs a{static_cast<const bf16*>(dy), static_cast<const bf16*>(x), slab, bslab, Out, In, N, kPlain, 0, 0, 0, 0,
+             1, 1, 1, 1, 1, 1, 0, 0, In, 0};
+    gemm_tn(a, splits, cur());
+  });
 }
 
 // deterministic slab statistics: (pointer, parts) for bn_apply / bn_bwd_apply

@@ -17,31 +17,37 @@ from ..params import ParamSpec
 from .base import LayerConfig, ParameterizedLayer
 
 
-class Conv2D(ParameterizedLayer):
-    type_name = "conv2d"
+class _ConvBase(ParameterizedLayer):
+    """What a 2-D convolution layer's geometry and parameters are, once for the three conv layers:
+    weights ``(Co, Ci / G, KH, KW)`` and an optional bias ``(Co,)``; dense ``G == 1``, depthwise
+    ``Ci == Co == G``. ``forward`` / ``backward`` here are the depthwise and grouped passes (they
+    differ in the ``ops`` entry only); :class:`Conv2D` overrides both."""
+    _depthwise = False
+    _weights_channels_last = True  # ParamSpec: the GPU operand layout [Co][KH][KW][Ci / G]
 
-    def __init__(self, in_channels: int, out_channels: int, kernel_h: int, kernel_w: int, stride_h: int = 1,
-                 stride_w: int = 1, pad_h: int = 0, pad_w: int = 0, use_bias: bool = True, name: str = "conv2d"):
+    def __init__(self, name, in_channels, out_channels, kernel_h, kernel_w, groups, stride_h, stride_w, pad_h, pad_w,
+                 use_bias):
         super().__init__(name)
-        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.in_channels, self.out_channels, self.groups = int(in_channels), int(out_channels), int(groups)
         self.kernel_h, self.kernel_w = int(kernel_h), int(kernel_w)
         self.stride_h, self.stride_w = int(stride_h), int(stride_w)
         self.pad_h, self.pad_w = int(pad_h), int(pad_w)
         self.use_bias = bool(use_bias)
-        # GPU fusion hooks set by the Sequential planner
-        self.emit_bn_stats = False
 
     # params ---------------------------------------------------------------------------
+    def _wshape(self):
+        return (self.out_channels, self.in_channels // self.groups, self.kernel_h, self.kernel_w)
+
     def param_specs(self):
-        s = [ParamSpec("weights", (self.out_channels, self.in_channels, self.kernel_h, self.kernel_w), True)]
+        s = [ParamSpec("weights", self._wshape(), self._weights_channels_last)]
         if self.use_bias:
             s.append(ParamSpec("bias", (self.out_channels, 1, 1, 1)))
         return s
 
     def init_values(self, gen):
-        fan_in = self.in_channels * self.kernel_h * self.kernel_w
+        fan_in = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # one group's fan-in
         bound = 1.0 / math.sqrt(fan_in)  # conv2d_layer.tpp:70-86
-        vals = [torch.empty(self.param_specs()[0].shape).uniform_(-bound, bound, generator=gen)]
+        vals = [torch.empty(self._wshape()).uniform_(-bound, bound, generator=gen)]
         if self.use_bias:
             vals.append(torch.empty((self.out_channels, 1, 1, 1)).uniform_(-bound, bound, generator=gen))
         return vals
@@ -57,16 +63,127 @@ class Conv2D(ParameterizedLayer):
     def _bias_vec(self):
         return self._params[1].view(-1) if self.use_bias else None
 
+    def _bias_grad(self):
+        return self._grads[1].view(-1) if self.use_bias else None
+
+    def _sp(self):
+        return (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
+
     # compute --------------------------------------------------------------------------
-    def forward(self, x, mb_id=0):
+    def _checked_input(self, x):
         if not self.initialized:
-            raise RuntimeError(f"Conv2D '{self.name}' must be initialized before forward")
+            raise RuntimeError(f"{type(self).__name__} '{self.name}' must be initialized before forward")
         x = self._to_layer_device(x)
         if x.shape[1] != self.in_channels:
-            raise ValueError(f"Conv2D '{self.name}': input has {x.shape[1]} channels, expected {self.in_channels}")
+            raise ValueError(f"{type(self).__name__} '{self.name}': input has {x.shape[1]} channels, expected "
+                             f"{self.in_channels}")
+        return x
+
+    def _pop_input(self, mb_id):
+        x = self._cache.pop(mb_id, None)
+        if x is None:
+            raise RuntimeError(f"{type(self).__name__} '{self.name}': no cached input for micro-batch {mb_id}")
+        return x
+
+    @staticmethod
+    def _cpu_add_to(dx, add_to):
+        if dx is not None and add_to is not None:
+            from ...ops import cpu
+            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
+        return dx
+
+    def forward(self, x, mb_id=0):
+        x = self._checked_input(x)
+        st, pd = self._sp()
         if x.is_cuda:
             from ...ops import hip
-            st, pd = (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
+            x = hip.to_act(x, self.compute_dtype)
+            if self._depthwise:
+                y = hip.dwconv2d_fwd(x, self.weight_operand(0), self._bias_vec(), st, pd)
+            else:
+                y = hip.gconv2d_fwd(x, self.weight_operand(0), self._bias_vec(), st, pd, self.groups)
+        else:
+            from ...ops import cpu
+            if self._depthwise:
+                y = cpu.depthwise_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd)
+            else:
+                y = cpu.grouped_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd, self.groups)
+        self._cache[mb_id] = x
+        return y
+
+    def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
+        x = self._pop_input(mb_id)
+        grad = grad.to(x.device)
+        st, pd = self._sp()
+        gw, gb = self._grads[0], self._bias_grad()
+        if x.is_cuda:
+            from ...ops import hip
+            g = hip.to_act(grad, self.compute_dtype)
+            if self._depthwise:
+                hip.dwconv2d_wgrad(g, x, self.weights.shape, st, pd, gw, gb)
+            else:
+                hip.gconv2d_wgrad(g, x, self.weights.shape, st, pd, self.groups, gw, gb)
+            if not self.needs_input_grad:
+                return None
+            res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
+            if self._depthwise:
+                return hip.dwconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, residual=res)
+            return hip.gconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, self.groups, residual=res)
+        from ...ops import cpu
+        if self._depthwise:
+            dx = cpu.depthwise_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, gw, gb,
+                                          need_dx=self.needs_input_grad)
+        else:
+            dx = cpu.grouped_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self.groups, gw, gb,
+                                        need_dx=self.needs_input_grad)
+        return self._cpu_add_to(dx, add_to)
+
+    # shapes / cost ----------------------------------------------------------------------
+    def _out_hw(self, h, w):
+        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
+                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
+
+    def compute_output_shape(self, s):
+        oh, ow = self._out_hw(s[2], s[3])
+        return [s[0], self.out_channels, oh, ow]
+
+    def _flops(self, s, per_mac):
+        oh, ow = self._out_hw(s[2], s[3])
+        out = s[0] * oh * ow
+        k = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # a dense conv's, divided by G
+        f = per_mac * self.out_channels * k * out
+        if self.use_bias:
+            f += self.out_channels * out
+        return f
+
+    def forward_flops(self, s):
+        return self._flops(s, 2)
+
+    def backward_flops(self, s):
+        return self._flops(s, 4)  # weight grad + input grad
+
+    def _geometry_config(self):
+        """stride_h .. use_bias, after the subclass's channel and kernel keys (the saved key order)"""
+        return dict(stride_h=self.stride_h, stride_w=self.stride_w, pad_h=self.pad_h, pad_w=self.pad_w,
+                    use_bias=self.use_bias)
+
+
+class Conv2D(_ConvBase):
+    type_name = "conv2d"
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_h: int, kernel_w: int, stride_h: int = 1,
+                 stride_w: int = 1, pad_h: int = 0, pad_w: int = 0, use_bias: bool = True, name: str = "conv2d"):
+        super().__init__(name, in_channels, out_channels, kernel_h, kernel_w, 1, stride_h, stride_w, pad_h, pad_w,
+                         use_bias)
+        # GPU fusion hooks set by the Sequential planner
+        self.emit_bn_stats = False
+
+    # compute --------------------------------------------------------------------------
+    def forward(self, x, mb_id=0):
+        x = self._checked_input(x)
+        st, pd = self._sp()
+        if x.is_cuda:
+            from ...ops import hip
             if (self.compute_dtype == torch.bfloat16 and not self.needs_input_grad
                     and hip.stem_ok(x, self.weights.shape, st, pd)):
                 # RGB stem straight from the fp32 NCHW input (stem.hip): no layout/pad pass
@@ -84,36 +201,33 @@ class Conv2D(ParameterizedLayer):
             else:
                 xa = hip.to_act(x, self.compute_dtype)
                 w = self.weight_operand(0)
-            y, partial = hip.conv2d_fwd(xa, w, self._bias_vec(), (self.stride_h, self.stride_w),
-                                        (self.pad_h, self.pad_w), stats=self.emit_bn_stats and self.training)
+            y, partial = hip.conv2d_fwd(xa, w, self._bias_vec(), st, pd, stats=self.emit_bn_stats and self.training)
             if partial is not None:
                 y._bn_partial = partial
             self._cache[mb_id] = (xa, tuple(x.shape))
             return y
         from ...ops import cpu
-        y = cpu.conv2d_fwd(x, self.weights, self._bias_vec(), (self.stride_h, self.stride_w), (self.pad_h, self.pad_w))
+        y = cpu.conv2d_fwd(x, self.weights, self._bias_vec(), st, pd)
         self._cache[mb_id] = x
         return y
 
     def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
-        x = self._cache.pop(mb_id, None)
-        if x is None:
-            raise RuntimeError(f"Conv2D '{self.name}': no cached input for micro-batch {mb_id}")
+        x = self._pop_input(mb_id)
         stem = isinstance(x, tuple) and len(x) == 3
         if isinstance(x, tuple):
             x, x_shape = x[0], x[1]
         else:
             x_shape = tuple(x.shape)
         grad = grad.to(x.device)
+        st, pd = self._sp()
+        gb = self._bias_grad()
         if x.is_cuda:
             from ...ops import hip
             g = hip.to_act(grad, self.compute_dtype)
-            gb = self._grads[1].view(-1) if self.use_bias else None
             if stem:  # forward ran stem.hip (never with an input gradient)
                 hip.stem_conv_wgrad(g, x, self._grads[0], gb)
                 return None
-            hip.conv2d_wgrad(g, x, self.weights.shape, (self.stride_h, self.stride_w), (self.pad_h, self.pad_w),
-                             self._grads[0], gb)
+            hip.conv2d_wgrad(g, x, self.weights.shape, st, pd, self._grads[0], gb)
             if not self.needs_input_grad:
                 return None
             if getattr(self, "_wt_valid", False):
@@ -121,48 +235,16 @@ class Conv2D(ParameterizedLayer):
             else:
                 wt = hip.conv_weight_t(self.weight_operand(0), dtype=self.compute_dtype)
             res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
-            return hip.conv2d_dgrad(g, wt, x_shape, (self.stride_h, self.stride_w), (self.pad_h, self.pad_w),
-                                    residual=res, bnb=self._bnb_request)
+            return hip.conv2d_dgrad(g, wt, x_shape, st, pd, residual=res, bnb=self._bnb_request)
         from ...ops import cpu
-        st, pd = (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
-        dx = cpu.conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self._grads[0],
-                            self._grads[1].view(-1) if self.use_bias else None, need_dx=self.needs_input_grad)
-        if dx is not None and add_to is not None:
-            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
-        return dx
-
-    # shapes / cost ----------------------------------------------------------------------
-    def _out_hw(self, h, w):
-        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
-                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
-
-    def compute_output_shape(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        return [s[0], self.out_channels, oh, ow]
-
-    def forward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        k = self.in_channels * self.kernel_h * self.kernel_w
-        f = 2 * self.out_channels * k * out
-        if self.use_bias:
-            f += self.out_channels * out
-        return f
-
-    def backward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        k = self.in_channels * self.kernel_h * self.kernel_w
-        f = 4 * self.out_channels * k * out  # weight grad + input grad
-        if self.use_bias:
-            f += self.out_channels * out
-        return f
+        dx = cpu.conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self._grads[0], gb,
+                            need_dx=self.needs_input_grad)
+        return self._cpu_add_to(dx, add_to)
 
     def get_config(self):
         return LayerConfig(self.name, dict(
             in_channels=self.in_channels, out_channels=self.out_channels, kernel_h=self.kernel_h,
-            kernel_w=self.kernel_w, stride_h=self.stride_h, stride_w=self.stride_w, pad_h=self.pad_h,
-            pad_w=self.pad_w, use_bias=self.use_bias, optimized="mfma"), self.type_name)
+            kernel_w=self.kernel_w, **self._geometry_config(), optimized="mfma"), self.type_name)
 
     @staticmethod
     def from_config(cfg):
@@ -172,122 +254,26 @@ class Conv2D(ParameterizedLayer):
                       cfg.name or "conv2d")
 
 
-class DepthwiseConv2D(ParameterizedLayer):
+class DepthwiseConv2D(_ConvBase):
     """Depthwise convolution: one KHxKW filter per channel (``F.conv2d(groups=C)``, channel
     multiplier 1). Not in the reference. GPU path: the streaming kernels of dwconv.hip (no MFMA:
-    KH*KW MACs per element, bandwidth-bound). Deliberately not a :class:`Conv2D`: the fusion
-    planner sees it as ``FK_OTHER`` — it emits no BatchNorm statistics, ignores ``_bnb_request``
-    and needs no transposed weight operand."""
+    KH*KW MACs per element, bandwidth-bound). Shares ``_ConvBase``; not a :class:`Conv2D` for the
+    planner: it sees ``FK_OTHER`` — the layer emits no BatchNorm statistics, ignores
+    ``_bnb_request`` and needs no transposed weight operand."""
     type_name = "depthwise_conv2d"
+    _depthwise = True
+    _weights_channels_last = False  # (C, 1, KH, KW): both layouts are the same bytes [C][KH][KW]
 
     def __init__(self, channels: int, kernel_h: int, kernel_w: int, stride_h: int = 1, stride_w: int = 1,
                  pad_h: int = 0, pad_w: int = 0, use_bias: bool = True, name: str = "depthwise_conv2d"):
-        super().__init__(name)
-        self.channels = int(channels)
-        self.kernel_h, self.kernel_w = int(kernel_h), int(kernel_w)
-        self.stride_h, self.stride_w = int(stride_h), int(stride_w)
-        self.pad_h, self.pad_w = int(pad_h), int(pad_w)
-        self.use_bias = bool(use_bias)
-
-    # params ---------------------------------------------------------------------------
-    def param_specs(self):
-        s = [ParamSpec("weights", (self.channels, 1, self.kernel_h, self.kernel_w))]
-        if self.use_bias:
-            s.append(ParamSpec("bias", (self.channels, 1, 1, 1)))
-        return s
-
-    def init_values(self, gen):
-        bound = 1.0 / math.sqrt(self.kernel_h * self.kernel_w)  # Conv2D's rule, fan-in of one channel
-        vals = [torch.empty((self.channels, 1, self.kernel_h, self.kernel_w)).uniform_(-bound, bound, generator=gen)]
-        if self.use_bias:
-            vals.append(torch.empty((self.channels, 1, 1, 1)).uniform_(-bound, bound, generator=gen))
-        return vals
-
-    @property
-    def weights(self):
-        return self._params[0]
-
-    @property
-    def bias(self):
-        return self._params[1] if self.use_bias else None
-
-    def _bias_vec(self):
-        return self._params[1].view(-1) if self.use_bias else None
-
-    def _sp(self):
-        return (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
-
-    # compute --------------------------------------------------------------------------
-    def forward(self, x, mb_id=0):
-        if not self.initialized:
-            raise RuntimeError(f"DepthwiseConv2D '{self.name}' must be initialized before forward")
-        x = self._to_layer_device(x)
-        if x.shape[1] != self.channels:
-            raise ValueError(f"DepthwiseConv2D '{self.name}': input has {x.shape[1]} channels, expected "
-                             f"{self.channels}")
-        st, pd = self._sp()
-        if x.is_cuda:
-            from ...ops import hip
-            xa = hip.to_act(x, self.compute_dtype)
-            y = hip.dwconv2d_fwd(xa, self.weight_operand(0), self._bias_vec(), st, pd)
-            self._cache[mb_id] = xa
-            return y
-        from ...ops import cpu
-        y = cpu.depthwise_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd)
-        self._cache[mb_id] = x
-        return y
-
-    def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
-        x = self._cache.pop(mb_id, None)
-        if x is None:
-            raise RuntimeError(f"DepthwiseConv2D '{self.name}': no cached input for micro-batch {mb_id}")
-        grad = grad.to(x.device)
-        st, pd = self._sp()
-        gb = self._grads[1].view(-1) if self.use_bias else None
-        if x.is_cuda:
-            from ...ops import hip
-            g = hip.to_act(grad, self.compute_dtype)
-            hip.dwconv2d_wgrad(g, x, self.weights.shape, st, pd, self._grads[0], gb)
-            if not self.needs_input_grad:
-                return None
-            res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
-            return hip.dwconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, residual=res)
-        from ...ops import cpu
-        dx = cpu.depthwise_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self._grads[0], gb,
-                                      need_dx=self.needs_input_grad)
-        if dx is not None and add_to is not None:
-            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
-        return dx
-
-    # shapes / cost ----------------------------------------------------------------------
-    def _out_hw(self, h, w):
-        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
-                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
-
-    def compute_output_shape(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        return [s[0], self.channels, oh, ow]
-
-    def forward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        f = 2 * self.channels * self.kernel_h * self.kernel_w * out
-        if self.use_bias:
-            f += self.channels * out
-        return f
-
-    def backward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        f = 4 * self.channels * self.kernel_h * self.kernel_w * out  # weight grad + input grad
-        if self.use_bias:
-            f += self.channels * out
-        return f
+        super().__init__(name, channels, channels, kernel_h, kernel_w, channels, stride_h, stride_w, pad_h, pad_w,
+                         use_bias)
+        self.channels = self.in_channels
 
     def get_config(self):
         return LayerConfig(self.name, dict(
-            channels=self.channels, kernel_h=self.kernel_h, kernel_w=self.kernel_w, stride_h=self.stride_h,
-            stride_w=self.stride_w, pad_h=self.pad_h, pad_w=self.pad_w, use_bias=self.use_bias), self.type_name)
+            channels=self.channels, kernel_h=self.kernel_h, kernel_w=self.kernel_w, **self._geometry_config()),
+            self.type_name)
 
     @staticmethod
     def from_config(cfg):
@@ -297,23 +283,19 @@ class DepthwiseConv2D(ParameterizedLayer):
                                cfg.name or "depthwise_conv2d")
 
 
-class GroupedConv2D(ParameterizedLayer):
+class GroupedConv2D(_ConvBase):
     """Grouped convolution, 1 < groups < channels (``F.conv2d(groups=G)``): output channel co reads
     the ``in_channels / groups`` input channels of group ``co // (out_channels / groups)``. Not in
     the reference. GPU path: the MFMA implicit-GEMM kernels of gconv.hip, one launch per pass over
-    all groups. A separate class like :class:`DepthwiseConv2D`: the fusion planner sees it as
-    ``FK_OTHER`` — it emits no BatchNorm statistics and ignores ``_bnb_request``."""
+    all groups. Shares ``_ConvBase``; not a :class:`Conv2D` for the planner: it sees ``FK_OTHER`` —
+    the layer emits no BatchNorm statistics and ignores ``_bnb_request``."""
     type_name = "grouped_conv2d"
 
     def __init__(self, in_channels: int, out_channels: int, kernel_h: int, kernel_w: int, groups: int,
                  stride_h: int = 1, stride_w: int = 1, pad_h: int = 0, pad_w: int = 0, use_bias: bool = True,
                  name: str = "grouped_conv2d"):
-        super().__init__(name)
-        self.in_channels, self.out_channels, self.groups = int(in_channels), int(out_channels), int(groups)
-        self.kernel_h, self.kernel_w = int(kernel_h), int(kernel_w)
-        self.stride_h, self.stride_w = int(stride_h), int(stride_w)
-        self.pad_h, self.pad_w = int(pad_h), int(pad_w)
-        self.use_bias = bool(use_bias)
+        super().__init__(name, in_channels, out_channels, kernel_h, kernel_w, groups, stride_h, stride_w, pad_h,
+                         pad_w, use_bias)
         if self.groups == 1:
             raise ValueError(f"GroupedConv2D '{name}': groups == 1, use Conv2D")
         if self.groups == self.in_channels == self.out_channels:
@@ -323,112 +305,10 @@ class GroupedConv2D(ParameterizedLayer):
             raise ValueError(f"GroupedConv2D '{name}': groups {self.groups} must divide in_channels "
                              f"{self.in_channels} and out_channels {self.out_channels}")
 
-    # params ---------------------------------------------------------------------------
-    def _wshape(self):
-        return (self.out_channels, self.in_channels // self.groups, self.kernel_h, self.kernel_w)
-
-    def param_specs(self):
-        s = [ParamSpec("weights", self._wshape(), True)]
-        if self.use_bias:
-            s.append(ParamSpec("bias", (self.out_channels, 1, 1, 1)))
-        return s
-
-    def init_values(self, gen):
-        fan_in = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # Conv2D's rule, one group's fan-in
-        bound = 1.0 / math.sqrt(fan_in)
-        vals = [torch.empty(self._wshape()).uniform_(-bound, bound, generator=gen)]
-        if self.use_bias:
-            vals.append(torch.empty((self.out_channels, 1, 1, 1)).uniform_(-bound, bound, generator=gen))
-        return vals
-
-    @property
-    def weights(self):
-        return self._params[0]
-
-    @property
-    def bias(self):
-        return self._params[1] if self.use_bias else None
-
-    def _bias_vec(self):
-        return self._params[1].view(-1) if self.use_bias else None
-
-    def _sp(self):
-        return (self.stride_h, self.stride_w), (self.pad_h, self.pad_w)
-
-    # compute --------------------------------------------------------------------------
-    def forward(self, x, mb_id=0):
-        if not self.initialized:
-            raise RuntimeError(f"GroupedConv2D '{self.name}' must be initialized before forward")
-        x = self._to_layer_device(x)
-        if x.shape[1] != self.in_channels:
-            raise ValueError(f"GroupedConv2D '{self.name}': input has {x.shape[1]} channels, expected "
-                             f"{self.in_channels}")
-        st, pd = self._sp()
-        if x.is_cuda:
-            from ...ops import hip
-            xa = hip.to_act(x, self.compute_dtype)
-            y = hip.gconv2d_fwd(xa, self.weight_operand(0), self._bias_vec(), st, pd, self.groups)
-            self._cache[mb_id] = xa
-            return y
-        from ...ops import cpu
-        y = cpu.grouped_conv2d_fwd(x, self.weights, self._bias_vec(), st, pd, self.groups)
-        self._cache[mb_id] = x
-        return y
-
-    def backward(self, grad, mb_id=0, add_to: Optional[torch.Tensor] = None):
-        x = self._cache.pop(mb_id, None)
-        if x is None:
-            raise RuntimeError(f"GroupedConv2D '{self.name}': no cached input for micro-batch {mb_id}")
-        grad = grad.to(x.device)
-        st, pd = self._sp()
-        gb = self._grads[1].view(-1) if self.use_bias else None
-        if x.is_cuda:
-            from ...ops import hip
-            g = hip.to_act(grad, self.compute_dtype)
-            hip.gconv2d_wgrad(g, x, self.weights.shape, st, pd, self.groups, self._grads[0], gb)
-            if not self.needs_input_grad:
-                return None
-            res = hip.to_act(add_to, self.compute_dtype) if add_to is not None else None
-            return hip.gconv2d_dgrad(g, self.weight_operand(0), tuple(x.shape), st, pd, self.groups, residual=res)
-        from ...ops import cpu
-        dx = cpu.grouped_conv2d_bwd(x, self.weights, grad.to(x.dtype), st, pd, self.groups, self._grads[0], gb,
-                                    need_dx=self.needs_input_grad)
-        if dx is not None and add_to is not None:
-            cpu.elementwise(0, 0, dx, add_to.to(dx.dtype), out=dx)
-        return dx
-
-    # shapes / cost ----------------------------------------------------------------------
-    def _out_hw(self, h, w):
-        return ((h + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
-                (w + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
-
-    def compute_output_shape(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        return [s[0], self.out_channels, oh, ow]
-
-    def forward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        k = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w  # a dense conv's, divided by G
-        f = 2 * self.out_channels * k * out
-        if self.use_bias:
-            f += self.out_channels * out
-        return f
-
-    def backward_flops(self, s):
-        oh, ow = self._out_hw(s[2], s[3])
-        out = s[0] * oh * ow
-        k = (self.in_channels // self.groups) * self.kernel_h * self.kernel_w
-        f = 4 * self.out_channels * k * out  # weight grad + input grad
-        if self.use_bias:
-            f += self.out_channels * out
-        return f
-
     def get_config(self):
         return LayerConfig(self.name, dict(
             in_channels=self.in_channels, out_channels=self.out_channels, kernel_h=self.kernel_h,
-            kernel_w=self.kernel_w, groups=self.groups, stride_h=self.stride_h, stride_w=self.stride_w,
-            pad_h=self.pad_h, pad_w=self.pad_w, use_bias=self.use_bias), self.type_name)
+            kernel_w=self.kernel_w, groups=self.groups, **self._geometry_config()), self.type_name)
 
     @staticmethod
     def from_config(cfg):

@@ -192,16 +192,21 @@ def conv2d_fwd(x, w, bias, stride, pad):
     return y
 
 
+def _bwd_dx(x, grad_w, grad_b, need_dx):
+    """a conv backward's dx buffer (None without need_dx), after the accumulators' contiguity check"""
+    for g in (grad_w, grad_b):
+        if g is not None and not g.is_contiguous():
+            raise ValueError("gradient accumulators must be contiguous")
+    return torch.empty_like(x) if need_dx else None
+
+
 def conv2d_bwd(x, w, dy, stride, pad, grad_w, grad_b=None, need_dx=True):
     """grad_w (+)= dW, grad_b (+)= sum(dy); returns dx (or None). grad_w/grad_b must be contiguous."""
     x, w, dy = _c(x), _c(w), _c(dy)
     _same(x, w, dy, grad_w, grad_b)
     N, Ci, H, W = x.shape
     Co, _, KH, KW = w.shape
-    for g in (grad_w, grad_b):
-        if g is not None and not g.is_contiguous():
-            raise ValueError("gradient accumulators must be contiguous")
-    dx = torch.empty_like(x) if need_dx else None
+    dx = _bwd_dx(x, grad_w, grad_b, need_dx)
     C().conv2d_bwd(dt(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), p(dx), grad_w.data_ptr(), p(grad_b), N, Ci, H, W,
                    Co, KH, KW, stride[0], stride[1], pad[0], pad[1])
     return dx
@@ -233,10 +238,7 @@ def depthwise_conv2d_bwd(x, w, dy, stride, pad, grad_w, grad_b=None, need_dx=Tru
     OH, OW = _odim(H, KH, stride[0], pad[0]), _odim(W, KW, stride[1], pad[1])
     if tuple(w.shape[:2]) != (Cc, 1) or tuple(dy.shape) != (N, Cc, OH, OW):
         raise ValueError(f"depthwise_conv2d_bwd: x {tuple(x.shape)}, w {tuple(w.shape)}, dy {tuple(dy.shape)}")
-    for g in (grad_w, grad_b):
-        if g is not None and not g.is_contiguous():
-            raise ValueError("gradient accumulators must be contiguous")
-    dx = torch.empty_like(x) if need_dx else None
+    dx = _bwd_dx(x, grad_w, grad_b, need_dx)
     C().depthwise_conv2d_bwd(dt(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), p(dx), grad_w.data_ptr(), p(grad_b), N,
                              Cc, H, W, KH, KW, stride[0], stride[1], pad[0], pad[1])
     return dx
@@ -272,10 +274,7 @@ def grouped_conv2d_bwd(x, w, dy, stride, pad, groups, grad_w, grad_b=None, need_
     N, Cc, H, W, Co, KH, KW, OH, OW = _grouped_geom("grouped_conv2d_bwd", x, w, groups, stride, pad)
     if tuple(dy.shape) != (N, Co, OH, OW):
         raise ValueError(f"grouped_conv2d_bwd: x {tuple(x.shape)}, w {tuple(w.shape)}, dy {tuple(dy.shape)}")
-    for g in (grad_w, grad_b):
-        if g is not None and not g.is_contiguous():
-            raise ValueError("gradient accumulators must be contiguous")
-    dx = torch.empty_like(x) if need_dx else None
+    dx = _bwd_dx(x, grad_w, grad_b, need_dx)
     C().grouped_conv2d_bwd(dt(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), p(dx), grad_w.data_ptr(), p(grad_b), N,
                            Cc, H, W, Co, groups, KH, KW, stride[0], stride[1], pad[0], pad[1])
     return dx

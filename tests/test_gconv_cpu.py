@@ -143,13 +143,16 @@ def test_layer_matches_autograd_and_honours_input_grad_flag():
     assert torch.allclose(dx, x.grad + add, rtol=1e-5, atol=1e-5)
     gw, gb = l.gradients()
     assert torch.allclose(gw, w.grad, rtol=1e-5, atol=1e-5) and torch.allclose(gb, b.grad, rtol=1e-5, atol=1e-5)
-    with pytest.raises(RuntimeError, match="no cached input"):
+    with pytest.raises(RuntimeError, match="^GroupedConv2D 'g': no cached input for micro-batch 1$"):
         l.backward(dy, 1)
     l.needs_input_grad = False
     l.forward(x.detach())
     assert l.backward(dy) is None
-    with pytest.raises(ValueError, match="channels"):
+    # the shared base's messages carry the concrete class name
+    with pytest.raises(ValueError, match="^GroupedConv2D 'g': input has 4 channels, expected 8$"):
         l.forward(torch.randn(1, 4, 7, 6))
+    with pytest.raises(RuntimeError, match="^GroupedConv2D 'cold' must be initialized before forward$"):
+        GroupedConv2D(8, 16, 3, 3, 2, name="cold").forward(torch.randn(1, 8, 7, 6))
 
 
 def _small_net():
