@@ -449,32 +449,6 @@ void hconv_workspace(HConvArgs& a) {
   }
 }
 
-// gathered-GEMM argument block (gemm2.hip) for a forward conv
-G2Args g2_fwd_args(const void* x, const void* w, void* y, const float* bias, const ConvShape& s) {
-  G2Args a{};
-  a.A = static_cast<const bf16*>(x);
-  a.B = static_cast<const bf16*>(w);
-  a.C = static_cast<bf16*>(y);
-  a.a_bytes = (unsigned)((long)s.N * s.H * s.W * s.C * 2);
-  a.b_bytes = (unsigned)((long)s.Co * s.KH * s.KW * s.C * 2);
-  a.M = s.N * s.OH * s.OW;
-  a.N = s.Co;
-  a.Cs = s.C;
-  a.H = s.H; a.W = s.W; a.GH = s.OH; a.GW = s.OW; a.SY = s.SH; a.SX = s.SW;
-  int t = 0;
-  for (int ky = 0; ky < s.KH; ++ky)
-    for (int kx = 0; kx < s.KW; ++kx, ++t) {
-      const int dy = ky - s.PH, dx = kx - s.PW;
-      a.tap_dy[t] = dy; a.tap_dx[t] = dx; a.tap_srcoff[t] = (dy * s.W + dx) * s.C; a.tap_b[t] = (ky * s.KW + kx) * s.C;
-    }
-  a.ntaps = t;
-  a.ldb = s.KH * s.KW * s.C;
-  a.ldc = s.Co;
-  a.OH = s.OH; a.OW = s.OW; a.OSY = 1; a.OSX = 1; a.ORY = 0; a.ORX = 0;
-  a.bias = bias;
-  return a;
-}
-
 // SecondaryStats scope: forward conv statistics go to the second slab workspace
 thread_local bool t_secondary = false;
 inline Slot fwd_stats_slot() { return t_secondary ? FWD_STATS2 : FWD_STATS; }
@@ -595,17 +569,11 @@ const float* conv_fwd(const void* x, const void* w, const float* bias, void* y, 
   };
   const int M = s.N * s.OH * s.OW;
   // the shared routing table (conv_route.cpp): the same kernels as the Python front end
-  const int route = conv_fwd_route(route_geom(s, want ? 1 : 0));
+  const ConvRouteGeom g = route_geom(s, want ? 1 : 0);
+  const int route = conv_fwd_route(g);
   rec("fwd", s, route, {{"bias", bias != nullptr}, {"stats", want}});
   if (route == ROUTE_HALO && xb < (1l << 31)) {
-    HConvArgs a{};
-    a.A = static_cast<const bf16*>(x); a.B = static_cast<const bf16*>(w); a.C = static_cast<bf16*>(y);
-    a.a_bytes = (unsigned)xb; a.b_bytes = (unsigned)wb;
-    a.NB = s.N; a.H = s.H; a.W = s.W; a.Cs = s.C; a.N = s.Co; a.ldb = s.KH * s.KW * s.C; a.ntaps = s.KH * s.KW;
-    for (int t = 0; t < a.ntaps; ++t) {
-      a.tap_dy[t] = t / s.KW - s.PH; a.tap_dx[t] = t % s.KW - s.PW; a.tap_b[t] = t * s.C;
-    }
-    a.bias = bias;
+    HConvArgs a = hconv_fwd_args(x, w, y, bias, g);
     if (want) a.stats = slab_of(hconv_stat_rows(s.N, s.H, s.W, s.C, s.Co, a.ntaps, 0));
     hconv_workspace(a);
     hconv(a, cur());
@@ -618,7 +586,7 @@ const float* conv_fwd(const void* x, const void* w, const float* bias, void* y, 
     return st;
   }
   if (route != ROUTE_GENERIC && xb < (1l << 31) && wb < (1l << 31)) {
-    G2Args a = g2_fwd_args(x, w, y, bias, s);
+    G2Args a = g2_fwd_args(x, w, y, bias, g);
     if (want) a.stats = slab_of(gemm_g2_stat_rows(M, s.Co));
     gemm_g2(a, cur());
     return a.stats;
@@ -671,20 +639,13 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
   }
   const long dyb = (long)s.N * s.OH * s.OW * s.Co * 2, wtb = (long)s.C * T * s.Co * 2;
   // shared routing table (conv_route.cpp); g1s mode 2: the streaming dgrad with the BN epilogue
-  const int route = conv_dgrad_route(route_geom(s, bnb ? 2 : 0));
+  const ConvRouteGeom g = route_geom(s, bnb ? 2 : 0);
+  const int route = conv_dgrad_route(g);
   rec("dgrad", s, route, {{"residual", residual != nullptr}, {"w_t", w_transposed}, {"bnb", bnb != nullptr},
                          {"bnb_mask", bnb != nullptr && bnb->y != nullptr}});
   if (route == ROUTE_HALO && dyb < (1l << 31)) {
     // transposed conv of a stride-1 'same' conv: tap (ky, kx) reads dy at (PH - ky, PW - kx)
-    HConvArgs a{};
-    a.A = static_cast<const bf16*>(dy); a.B = wt; a.C = static_cast<bf16*>(dx);
-    a.a_bytes = (unsigned)dyb; a.b_bytes = (unsigned)wtb;
-    a.NB = s.N; a.H = s.OH; a.W = s.OW; a.Cs = s.Co; a.N = s.C; a.ldb = T * s.Co; a.ntaps = T;
-    for (int t = 0; t < T; ++t) {
-      const int ky = t / s.KW, kx = t % s.KW;
-      a.tap_dy[t] = s.PH - ky; a.tap_dx[t] = s.PW - kx; a.tap_b[t] = t * s.Co;
-    }
-    a.residual = static_cast<const bf16*>(residual);
+    HConvArgs a = hconv_dgrad_args(dy, wt, dx, residual, g);
     if (bnb) {
       a.bnb = ba;
       a.stats = slab_of(hconv_stat_rows(s.N, s.OH, s.OW, s.Co, s.C, T, 0));
@@ -703,52 +664,18 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
   if (route != ROUTE_GENERIC && dyb < (1l << 31) && wtb < (1l << 31)) {
     // stride-phase decomposition: output phase (ry, rx) is a dense GEMM over the taps reaching
     // it; all phases are row classes of ONE grouped launch (phases no tap reaches write zeros)
-    struct Cls { int ry, rx, GH, GW, t0, nt; };
-    std::vector<Cls> cls;
-    G2Args a{};
-    int nt = 0;
+    const DgradPhases p = conv_dgrad_phases(g);
+    const std::vector<DgradPhase>& cls = p.phases;
+    if (p.taps.size() > 64) throw std::runtime_error("conv_dgrad: more than 64 taps");
     bool uniform = true;
-    for (int ry = 0; ry < s.SH; ++ry)
-      for (int rx = 0; rx < s.SW; ++rx) {
-        const int GH = (s.H - ry + s.SH - 1) / s.SH, GW = (s.W - rx + s.SW - 1) / s.SW;
-        if (GH <= 0 || GW <= 0) continue;
-        Cls c{ry, rx, GH, GW, nt, 0};
-        for (int ky = 0; ky < s.KH; ++ky) {
-          if ((ry + s.PH - ky) % s.SH) continue;
-          const int dyo = (ry + s.PH - ky) / s.SH;
-          for (int kx = 0; kx < s.KW; ++kx) {
-            if ((rx + s.PW - kx) % s.SW) continue;
-            const int dxo = (rx + s.PW - kx) / s.SW;
-            if (nt >= 64) throw std::runtime_error("conv_dgrad: more than 64 taps");
-            a.tap_dy[nt] = dyo; a.tap_dx[nt] = dxo; a.tap_srcoff[nt] = (dyo * s.OW + dxo) * s.Co;
-            a.tap_b[nt] = (ky * s.KW + kx) * s.Co;
-            ++nt;
-            ++c.nt;
-          }
-        }
-        if (!cls.empty() && (c.GH != cls[0].GH || c.GW != cls[0].GW)) uniform = false;
-        cls.push_back(c);
-      }
+    for (const DgradPhase& c : cls) uniform = uniform && c.GH == cls[0].GH && c.GW == cls[0].GW;
     const long rows = (long)s.N * (cls.empty() ? 0 : cls[0].GH * cls[0].GW);
     if (uniform && !cls.empty() && cls.size() <= 4 && (cls.size() == 1 || rows % 128 == 0)) {
-      a.A = static_cast<const bf16*>(dy); a.B = wt; a.C = static_cast<bf16*>(dx);
-      a.a_bytes = (unsigned)dyb; a.b_bytes = (unsigned)wtb;
-      a.M = (int)(rows * (long)cls.size()); a.N = s.C; a.Cs = s.Co;
-      a.H = s.OH; a.W = s.OW; a.GH = cls[0].GH; a.GW = cls[0].GW; a.SY = 1; a.SX = 1;
-      a.ntaps = nt; a.ldb = T * s.Co; a.ldc = s.C;
-      a.OH = s.H; a.OW = s.W; a.OSY = s.SH; a.OSX = s.SW; a.ORY = cls[0].ry; a.ORX = cls[0].rx;
-      a.residual = static_cast<const bf16*>(residual);
-      if (cls.size() > 1) {
-        a.ncls = (int)cls.size();
-        a.cls_rows = (int)rows;
-        for (size_t k = 0; k < cls.size(); ++k) {
-          a.cls_t0[k] = cls[k].t0; a.cls_nt[k] = cls[k].nt; a.cls_ory[k] = cls[k].ry; a.cls_orx[k] = cls[k].rx;
-        }
-      }
+      G2Args a = g2_dgrad_args(dy, wt, dx, residual, g, p);
       // the producing BatchNorm's mask + backward statistics in the epilogue when every stride
       // phase has taps (a zero-tap phase's rows are written by the fill path, not the MMA epilogue)
       bool all_taps = true;
-      for (const Cls& c : cls) all_taps = all_taps && c.nt > 0;
+      for (const DgradPhase& c : cls) all_taps = all_taps && c.nt > 0;
       if (bnb && all_taps) {
         a.bnb = ba;
         a.stats = slab_of(gemm_g2_stat_rows(a.M, s.C));
@@ -767,45 +694,28 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
 void conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const ConvShape& s) {
   const int Ng = s.KH * s.KW * s.C, P = s.N * s.OH * s.OW;
   const long dyb = (long)P * s.Co * 2, xb = (long)s.N * s.H * s.W * s.C * 2;
-  const int route = conv_wgrad_route(route_geom(s, -1));  // shared routing table (conv_route.cpp)
+  const ConvRouteGeom g = route_geom(s, -1);
+  const int route = conv_wgrad_route(g);  // shared routing table (conv_route.cpp)
   rec("wgrad", s, route, {{"bias", gb != nullptr}, {"deferred", g_defer}});
   const long n = (long)s.Co * Ng;
   if (route == ROUTE_HALO) {
     const int splits = hwgrad_splits(s.N, s.H, s.W, s.C, s.Co);
     wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
-      HWArgs a{};
-      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-      a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
-      a.NB = s.N; a.H = s.H; a.W = s.W; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
-      for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3 - 1; a.tap_dx[t] = t % 3 - 1; }
-      hwgrad(a, splits, cur());
+      hwgrad(hwgrad_args(dy, x, slab, bslab, g, false), splits, cur());
     });
     return;
   }
   if (route == ROUTE_HALO_S2) {  // 3x3 stride 2: the stride-2 halo kernel (dY grid OH x OW)
     const int splits = hwgrad_s2_splits(s.N, s.OH, s.OW, s.C, s.Co);
     wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
-      HWArgs a{};
-      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-      a.dy_bytes = (unsigned)dyb; a.x_bytes = (unsigned)xb;
-      a.NB = s.N; a.H = s.OH; a.W = s.OW; a.Cs = s.C; a.Co = s.Co; a.ntaps = 9;
-      hwgrad_s2(a, splits, cur());
+      hwgrad_s2(hwgrad_args(dy, x, slab, bslab, g, true), splits, cur());
     });
     return;
   }
   if (route == ROUTE_GEMM_G2 && dyb < (1l << 31) && xb < (1l << 31) && P < (1 << 24)) {
     const int splits = gemm_t2_splits(s.Co, Ng, P);
     wgrad_split(splits, n, s.Co, gw, gb, [&](float* slab, float* bslab) {
-      T2Args a{};
-      a.dY = static_cast<const bf16*>(dy); a.X = static_cast<const bf16*>(x); a.slab = slab; a.bias_slab = bslab;
-      a.a_bytes = (unsigned)dyb; a.b_bytes = (unsigned)xb;
-      a.M = s.Co; a.N = Ng; a.P = P; a.ldy = s.Co; a.Cs = s.C; a.H = s.H; a.W = s.W; a.GH = s.OH; a.GW = s.OW;
-      a.SY = s.SH; a.SX = s.SW;
-      int t = 0;
-      for (int ky = 0; ky < s.KH; ++ky)
-        for (int kx = 0; kx < s.KW; ++kx, ++t) { a.tap_dy[t] = ky - s.PH; a.tap_dx[t] = kx - s.PW; }
-      a.ntaps = t;
-      gemm_t2(a, splits, cur());
+      gemm_t2(t2_wgrad_args(dy, x, slab, bslab, g), splits, cur());
     });
     return;
   }

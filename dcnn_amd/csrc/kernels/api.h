@@ -358,3 +358,5 @@ struct AugBatchArgs {
 bool augment_batch_supported(int C, int H, int W);
 void augment_batch(const AugBatchArgs& a, hipStream_t s);
 }  // namespace dcnn
+
+#include "conv_args.h"  // the shared conv tap tables and argument-block fillers (both front ends)

@@ -22,32 +22,50 @@ template <typename T>
 static inline T P(uintptr_t x) { return reinterpret_cast<T>(x); }
 static inline hipStream_t S(uintptr_t x) { return reinterpret_cast<hipStream_t>(x); }
 
-static void bind_gemm_g2(uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M, int N, int Cs,
-                         int H, int W, int GH, int GW, int SY, int SX, std::vector<std::array<int, 4>> taps, int ldb,
-                         int ldc, int OH, int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual,
-                         uintptr_t stats, int relu, uintptr_t zero_ptr, int zero_n, std::array<uintptr_t, 4> bnb,
-                         uintptr_t stream, std::vector<std::array<int, 4>> classes = {}) {
+using Ptr4 = std::array<uintptr_t, 4>;
+// backward-BatchNorm fusion operands (y, x, mean, istd); all 0: off
+static BnbArgs bnb_of(const Ptr4& b) {
+  return BnbArgs{P<const bf16*>(b[0]), P<const bf16*>(b[1]), P<const float*>(b[2]), P<const float*>(b[3])};
+}
+
+// gathered GEMM (gemm2.hip; f32: the fp32 instances of gemm_f32.hip, fp32 operand / result pointers).
+// classes: (first tap, taps, ORY, ORX) per row class of a grouped launch (empty: one class)
+static void bind_gemm_g2(int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M, int N,
+                         int Cs, int H, int W, int GH, int GW, int SY, int SX, const ConvTaps& taps, int ldb, int ldc,
+                         int OH, int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual,
+                         uintptr_t stats, int relu, uintptr_t zero_ptr, int zero_n, Ptr4 bnb, uintptr_t stream,
+                         const std::vector<std::array<int, 4>>& classes) {
+  const char* who = f32 ? "gemm_g2f" : "gemm_g2";
+  if (f32 && bnb[1]) throw std::runtime_error("gemm_g2f: backward-BN epilogue fusion is bf16-only");
   G2Args a{};
-  // classes: (first tap, taps, ORY, ORX) per row class of a grouped launch (empty: one class)
-  if (classes.size() > 4) throw std::runtime_error("gemm_g2: at most 4 row classes");
-  a.ncls = (int)classes.size();
-  a.cls_rows = classes.empty() ? 0 : M / (int)classes.size();
-  for (size_t c = 0; c < classes.size(); ++c) {
-    a.cls_t0[c] = classes[c][0]; a.cls_nt[c] = classes[c][1]; a.cls_ory[c] = classes[c][2]; a.cls_orx[c] = classes[c][3];
-  }
-  a.bnb = BnbArgs{P<const bf16*>(bnb[0]), P<const bf16*>(bnb[1]), P<const float*>(bnb[2]), P<const float*>(bnb[3])};
   a.A = P<const bf16*>(A); a.B = P<const bf16*>(B); a.C = P<bf16*>(C);
   a.a_bytes = a_bytes; a.b_bytes = b_bytes;
   a.M = M; a.N = N; a.Cs = Cs; a.H = H; a.W = W; a.GH = GH; a.GW = GW; a.SY = SY; a.SX = SX;
-  if (taps.size() > 64) throw std::runtime_error("gemm_g2: more than 64 taps");
-  a.ntaps = (int)taps.size();
-  for (size_t i = 0; i < taps.size(); ++i) {
-    a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; a.tap_srcoff[i] = taps[i][2]; a.tap_b[i] = taps[i][3];
-  }
+  set_classes(a, classes, who);
+  set_taps(a, taps, who);
   a.ldb = ldb; a.ldc = ldc; a.OH = OH; a.OW = OW; a.OSY = OSY; a.OSX = OSX; a.ORY = ORY; a.ORX = ORX;
   a.bias = P<const float*>(bias); a.residual = P<const bf16*>(residual); a.stats = P<float*>(stats); a.relu = relu;
   a.zero_ptr = P<float*>(zero_ptr); a.zero_n = zero_n;
-  gemm_g2(a, S(stream));
+  a.bnb = bnb_of(bnb);
+  if (f32)
+    gemm_g2f(a, S(stream));
+  else
+    gemm_g2(a, S(stream));
+}
+
+// gathered transposed GEMM of the weight gradients (gemm2.hip gemm_t2; f32: gemm_f32.hip)
+static void bind_gemm_t2(int f32, uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned a_bytes,
+                         unsigned b_bytes, int M, int N, int Pn, int ldy, int Cs, int H, int W, int GH, int GW, int SY,
+                         int SX, const WgradTaps& taps, int splits, uintptr_t stream) {
+  T2Args a{};
+  a.dY = P<const bf16*>(dY); a.X = P<const bf16*>(X); a.slab = P<float*>(slab); a.bias_slab = P<float*>(bias_slab);
+  a.a_bytes = a_bytes; a.b_bytes = b_bytes; a.M = M; a.N = N; a.P = Pn; a.ldy = ldy; a.Cs = Cs;
+  a.H = H; a.W = W; a.GH = GH; a.GW = GW; a.SY = SY; a.SX = SX;
+  set_taps(a, taps, f32 ? "gemm_t2f" : "gemm_t2");
+  if (f32)
+    gemm_t2f(a, splits, S(stream));
+  else
+    gemm_t2(a, splits, S(stream));
 }
 
 PYBIND11_MODULE(_kernels, m) {
@@ -92,51 +110,28 @@ PYBIND11_MODULE(_kernels, m) {
                        float value, uintptr_t st) {
     pad_crop(P<const float*>(in), P<float*>(out), NC, H, W, OH, OW, top, left, value, S(st));
   });
+  // halo conv (hconv.hip) or, f32, the exact fp32 instances of the persistent halo conv (hconv3.hip:
+  // Cf / residual_f only, 9 taps; false = not covered, nothing launched). taps as conv_fwd_taps.
   m.def("hconv",
-        [](uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int NB, int H, int W, int Cs,
-           int N, int ldb, std::vector<std::array<int, 3>> taps, uintptr_t bias, uintptr_t residual, uintptr_t stats,
-           int relu, uintptr_t zero_ptr, int zero_n, std::array<uintptr_t, 4> bnb, uintptr_t Cf, uintptr_t residual_f,
-           int splits, uintptr_t part, uintptr_t tickets, uintptr_t stream) {
+        [](int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int NB, int H, int W,
+           int Cs, int N, int ldb, const ConvTaps& taps, uintptr_t bias, uintptr_t residual, uintptr_t stats, int relu,
+           uintptr_t zero_ptr, int zero_n, Ptr4 bnb, uintptr_t Cf, uintptr_t residual_f, int splits, uintptr_t part,
+           uintptr_t tickets, uintptr_t stream) {
+          if (f32 && taps.size() != 9) return false;
           HConvArgs a{};
           a.splits = splits; a.part = P<float*>(part); a.tickets = P<unsigned*>(tickets);
           a.Cf = P<float*>(Cf); a.residual_f = P<const float*>(residual_f);
-          a.bnb = BnbArgs{P<const bf16*>(bnb[0]), P<const bf16*>(bnb[1]), P<const float*>(bnb[2]), P<const float*>(bnb[3])};
+          a.bnb = bnb_of(bnb);
           a.zero_ptr = P<float*>(zero_ptr); a.zero_n = zero_n;
           a.A = P<const bf16*>(A); a.B = P<const bf16*>(B); a.C = P<bf16*>(C);
           a.a_bytes = a_bytes; a.b_bytes = b_bytes;
           a.NB = NB; a.H = H; a.W = W; a.Cs = Cs; a.N = N; a.ldb = ldb;
-          if (taps.size() > 9 || taps.empty()) throw std::runtime_error("hconv: 1..9 taps");
-          a.ntaps = (int)taps.size();
-          for (size_t i = 0; i < taps.size(); ++i) { a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; a.tap_b[i] = taps[i][2]; }
+          set_taps(a, taps, "hconv");
           a.bias = P<const float*>(bias); a.residual = P<const bf16*>(residual); a.stats = P<float*>(stats); a.relu = relu;
+          if (f32) return hconv3_f32_try(a, S(stream));
           hconv(a, S(stream));
+          return true;
         });
-  m.def("hconv3_f32",
-        [](uintptr_t A, uintptr_t B, unsigned a_bytes, unsigned b_bytes, int NB, int H, int W, int Cs, int N, int ldb,
-           std::vector<std::array<int, 3>> taps, uintptr_t bias, uintptr_t stats, int relu, uintptr_t zero_ptr,
-           int zero_n, uintptr_t Cf, uintptr_t residual_f, int splits, uintptr_t part, uintptr_t tickets,
-           uintptr_t stream, std::array<uintptr_t, 4> bnb) {
-          HConvArgs a{};
-          // backward-BatchNorm fusion: (y, x, mean, istd), y / x the BatchNorm's fp32 tensors
-          a.bnb.y = P<const bf16*>(bnb[0]); a.bnb.x = P<const bf16*>(bnb[1]);
-          a.bnb.mean = P<const float*>(bnb[2]); a.bnb.istd = P<const float*>(bnb[3]);
-          a.splits = splits; a.part = P<float*>(part); a.tickets = P<unsigned*>(tickets);
-          a.Cf = P<float*>(Cf); a.residual_f = P<const float*>(residual_f);
-          a.zero_ptr = P<float*>(zero_ptr); a.zero_n = zero_n;
-          a.A = P<const bf16*>(A); a.B = P<const bf16*>(B);
-          a.a_bytes = a_bytes; a.b_bytes = b_bytes;
-          a.NB = NB; a.H = H; a.W = W; a.Cs = Cs; a.N = N; a.ldb = ldb;
-          if (taps.size() != 9) return false;
-          a.ntaps = 9;
-          for (size_t i = 0; i < taps.size(); ++i) { a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; a.tap_b[i] = taps[i][2]; }
-          a.bias = P<const float*>(bias); a.stats = P<float*>(stats); a.relu = relu;
-          return hconv3_f32_try(a, S(stream));
-        },
-        py::arg("A"), py::arg("B"), py::arg("a_bytes"), py::arg("b_bytes"), py::arg("NB"), py::arg("H"), py::arg("W"),
-        py::arg("Cs"), py::arg("N"), py::arg("ldb"), py::arg("taps"), py::arg("bias"), py::arg("stats"),
-        py::arg("relu"), py::arg("zero_ptr"), py::arg("zero_n"), py::arg("Cf"), py::arg("residual_f"),
-        py::arg("splits"), py::arg("part"), py::arg("tickets"), py::arg("stream"),
-        py::arg("bnb") = std::array<uintptr_t, 4>{0, 0, 0, 0});
   m.def("hconv3_f32_splits", &hconv3_f32_splits);
   m.def("hconv_supported", &hconv_supported);
   m.def("hconv_stat_rows", &hconv_stat_rows);
@@ -154,13 +149,15 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("hconv3_enable", &hconv3_enable);
   m.def("hconv_v3", &hconv_v3);
   m.def("hconv3_set_stamps", &hconv3_set_stamps);
+  // halo weight gradients (hwgrad.hip). kind 0: hwgrad (pairs: (dY offset, X offset, bias) channel
+  // windows of rows ldy / ldx wide; none: the plain wgrad), 1: hwgrad_s2 (no tap table), 2: hwgrad_f32
   m.def("hwgrad",
-        [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned dy_bytes, unsigned x_bytes, int NB,
-           int H, int W, int Cs, int Co, std::vector<std::array<int, 2>> taps, int splits, int ldy, int ldx,
-           std::vector<std::array<int, 3>> pairs, uintptr_t stream) {
+        [](int kind, uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned dy_bytes,
+           unsigned x_bytes, int NB, int H, int W, int Cs, int Co, const WgradTaps& taps, int splits, int ldy, int ldx,
+           const std::vector<std::array<int, 3>>& pairs, uintptr_t stream) {
           HWArgs a{};
           if (pairs.size() > 3) throw std::runtime_error("hwgrad: at most 3 operand pairs");
-          a.npairs = (int)pairs.size(); a.ldy = ldy; a.ldx = ldx;  // no pairs: the plain wgrad
+          a.npairs = (int)pairs.size(); a.ldy = ldy; a.ldx = ldx;
           for (size_t q = 0; q < pairs.size(); ++q) {
             a.pair_yoff[q] = pairs[q][0]; a.pair_xoff[q] = pairs[q][1]; a.pair_bias[q] = pairs[q][2];
           }
@@ -168,36 +165,20 @@ PYBIND11_MODULE(_kernels, m) {
           a.bias_slab = P<float*>(bias_slab);
           a.dy_bytes = dy_bytes; a.x_bytes = x_bytes;
           a.NB = NB; a.H = H; a.W = W; a.Cs = Cs; a.Co = Co;
-          if (taps.size() > 9 || taps.empty()) throw std::runtime_error("hwgrad: 1..9 taps");
-          a.ntaps = (int)taps.size();
-          for (size_t i = 0; i < taps.size(); ++i) { a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; }
-          hwgrad(a, splits, S(stream));
+          if (kind == 1) {
+            a.ntaps = 9;
+            hwgrad_s2(a, splits, S(stream));
+            return;
+          }
+          set_taps(a, taps, "hwgrad");
+          if (kind == 2)
+            hwgrad_f32(a, splits, S(stream));
+          else
+            hwgrad(a, splits, S(stream));
         });
   m.def("hwgrad_supported", &hwgrad_supported);
   m.def("hwgrad_s2_supported", &hwgrad_s2_supported);
   m.def("hwgrad_s2_splits", &hwgrad_s2_splits);
-  m.def("hwgrad_s2",
-        [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned dy_bytes, unsigned x_bytes, int NB,
-           int H, int W, int Cs, int Co, int splits, uintptr_t stream) {
-          HWArgs a{};
-          a.dY = P<const bf16*>(dY); a.X = P<const bf16*>(X); a.slab = P<float*>(slab);
-          a.bias_slab = P<float*>(bias_slab);
-          a.dy_bytes = dy_bytes; a.x_bytes = x_bytes;
-          a.NB = NB; a.H = H; a.W = W; a.Cs = Cs; a.Co = Co; a.ntaps = 9;
-          hwgrad_s2(a, splits, S(stream));
-        });
-  m.def("hwgrad_f32",
-        [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned dy_bytes, unsigned x_bytes, int NB,
-           int H, int W, int Cs, int Co, int splits, uintptr_t stream) {
-          HWArgs a{};
-          a.dY = P<const bf16*>(dY); a.X = P<const bf16*>(X); a.slab = P<float*>(slab);
-          a.bias_slab = P<float*>(bias_slab);
-          a.dy_bytes = dy_bytes; a.x_bytes = x_bytes;
-          a.NB = NB; a.H = H; a.W = W; a.Cs = Cs; a.Co = Co;
-          a.ntaps = 9;
-          for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3 - 1; a.tap_dx[t] = t % 3 - 1; }
-          hwgrad_f32(a, splits, S(stream));
-        });
   m.def("hwgrad_f32_supported", &hwgrad_f32_supported);
   m.def("hwgrad_f32_splits", &hwgrad_f32_splits);
   m.def("split3_bf16", [](uintptr_t in, uintptr_t out, long rows, int C, int pattern, uintptr_t st) {
@@ -205,62 +186,48 @@ PYBIND11_MODULE(_kernels, m) {
   });
   m.def("hwgrad_splits", &hwgrad_splits);
   m.def("hwgrad_set_version", &hwgrad_set_version);
-  m.def("gemm_g2f",
-        [](uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M, int N, int Cs, int H,
-           int W, int GH, int GW, int SY, int SX, std::vector<std::array<int, 4>> taps, int ldb, int ldc, int OH,
-           int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual, uintptr_t stats, int relu,
-           uintptr_t zero_ptr, int zero_n, std::array<uintptr_t, 4> bnb, uintptr_t stream) {
-          G2Args a{};  // fp32 operands (pointers reinterpreted by the kernel)
-          if (bnb[1]) throw std::runtime_error("gemm_g2f: backward-BN epilogue fusion is bf16-only");
-          a.A = P<const bf16*>(A); a.B = P<const bf16*>(B); a.C = P<bf16*>(C);
-          a.a_bytes = a_bytes; a.b_bytes = b_bytes;
-          a.M = M; a.N = N; a.Cs = Cs; a.H = H; a.W = W; a.GH = GH; a.GW = GW; a.SY = SY; a.SX = SX;
-          if (taps.size() > 64) throw std::runtime_error("gemm_g2f: more than 64 taps");
-          a.ntaps = (int)taps.size();
-          for (size_t i = 0; i < taps.size(); ++i) {
-            a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; a.tap_srcoff[i] = taps[i][2]; a.tap_b[i] = taps[i][3];
-          }
-          a.ldb = ldb; a.ldc = ldc; a.OH = OH; a.OW = OW; a.OSY = OSY; a.OSX = OSX; a.ORY = ORY; a.ORX = ORX;
-          a.bias = P<const float*>(bias); a.residual = P<const bf16*>(residual); a.stats = P<float*>(stats); a.relu = relu;
-          a.zero_ptr = P<float*>(zero_ptr); a.zero_n = zero_n;
-          gemm_g2f(a, S(stream));
-        });
   m.def("gemm_g2f_stat_rows", &gemm_g2f_stat_rows);
   m.def("gemm_g2_set_splitk", &gemm_g2_set_splitk);  // (DCNN_G2_SPLITK at run time: tests / A/B)
   m.def("gemm_g2_splitk_enabled", &gemm_g2_splitk_enabled);
   m.def("set_f32_mode", &set_f32_mode);
   m.def("get_f32_mode", &get_f32_mode);
-  m.def("gemm_t2f",
-        [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, int M, int N, int Pn, int ldy, int Cs,
-           int H, int W, int GH, int GW, int SY, int SX, std::vector<std::array<int, 2>> taps, int splits,
-           uintptr_t stream) {
-          T2Args a{};
-          a.dY = P<const bf16*>(dY); a.X = P<const bf16*>(X); a.slab = P<float*>(slab); a.bias_slab = P<float*>(bias_slab);
-          a.M = M; a.N = N; a.P = Pn; a.ldy = ldy; a.Cs = Cs; a.H = H; a.W = W; a.GH = GH; a.GW = GW; a.SY = SY; a.SX = SX;
-          if (taps.size() > 64) throw std::runtime_error("gemm_t2f: more than 64 taps");
-          a.ntaps = (int)taps.size();
-          for (size_t i = 0; i < taps.size(); ++i) { a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; }
-          gemm_t2f(a, splits, S(stream));
-        });
   m.def("gemm_t2f_splits", &gemm_t2f_splits);
   m.def("conv_weight_transpose_f32", [](uintptr_t w, uintptr_t wt, int Co, int T_, int Ci, uintptr_t st) {
     conv_weight_transpose_f32(P<const float*>(w), P<float*>(wt), Co, T_, Ci, S(st));
   });
-  m.def("gemm_g2", [](uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M, int N, int Cs,
-                      int H, int W, int GH, int GW, int SY, int SX, std::vector<std::array<int, 4>> taps, int ldb,
-                      int ldc, int OH, int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual,
-                      uintptr_t stats, int relu, uintptr_t zero_ptr, int zero_n, std::array<uintptr_t, 4> bnb,
-                      uintptr_t stream) {
-    bind_gemm_g2(A, B, C, a_bytes, b_bytes, M, N, Cs, H, W, GH, GW, SY, SX, std::move(taps), ldb, ldc, OH, OW, OSY, OSX,
-                 ORY, ORX, bias, residual, stats, relu, zero_ptr, zero_n, bnb, stream, {});
+  m.def("gemm_g2", &bind_gemm_g2);
+  // C[M][N] = A[M][K] . B[N][K]^T with the gathered GEMM's epilogue: one tap, a 1 x 1 grid per row
+  m.def("gemm_g2_plain", [](int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M,
+                            int N, int K, uintptr_t bias, uintptr_t residual, uintptr_t stats, int relu,
+                            uintptr_t zero_ptr, int zero_n, uintptr_t stream) {
+    bind_gemm_g2(f32, A, B, C, a_bytes, b_bytes, M, N, K, 1, 1, 1, 1, 1, 1, {{0, 0, 0, 0}}, K, N, 1, 1, 1, 1, 0, 0, bias,
+                 residual, stats, relu, zero_ptr, zero_n, Ptr4{0, 0, 0, 0}, stream, {});
   });
-  // grouped row classes (strided-dgrad phases in one launch): classes = (first tap, taps, ORY, ORX)
-  m.def("gemm_g2_grouped", &bind_gemm_g2);
   m.def("gemm_g2_stat_rows", &gemm_g2_stat_rows);
   for (auto [name, fn] : {std::pair<const char*, int (*)(ConvRouteGeom)>{"conv_fwd_route", &conv_fwd_route},
                           {"conv_dgrad_route", &conv_dgrad_route}, {"conv_wgrad_route", &conv_wgrad_route}})
     m.def(name, [fn](int N, int C, int H, int W, int Co, int KH, int KW, int SH, int SW, int PH, int PW, int OH, int OW,
                      int g1s_mode) { return fn(ConvRouteGeom{N, C, H, W, Co, KH, KW, SH, SW, PH, PW, OH, OW, g1s_mode}); });
+  // the shared tap tables (conv_args.cpp)
+  m.def("conv_fwd_taps", [](int C, int W, int KH, int KW, int PH, int PW) {
+    ConvRouteGeom g{};
+    g.W = W; g.KH = KH; g.KW = KW; g.PH = PH; g.PW = PW;
+    return conv_fwd_taps(g, C);
+  });
+  m.def("conv_wgrad_taps", [](int KH, int KW, int PH, int PW) {
+    ConvRouteGeom g{};
+    g.KH = KH; g.KW = KW; g.PH = PH; g.PW = PW;
+    return conv_wgrad_taps(g);
+  });
+  // -> ((ry, rx, GH, GW, first tap, taps) per phase, flat tap table)
+  m.def("conv_dgrad_phases", [](int H, int W, int OW, int Co, int KH, int KW, int SH, int SW, int PH, int PW) {
+    ConvRouteGeom g{};
+    g.H = H; g.W = W; g.OW = OW; g.Co = Co; g.KH = KH; g.KW = KW; g.SH = SH; g.SW = SW; g.PH = PH; g.PW = PW;
+    const DgradPhases p = conv_dgrad_phases(g);
+    std::vector<std::array<int, 6>> ph;
+    for (const DgradPhase& c : p.phases) ph.push_back({c.ry, c.rx, c.GH, c.GW, c.t0, c.nt});
+    return std::make_pair(ph, p.taps);
+  });
   m.attr("ROUTE_GENERIC") = (int)ROUTE_GENERIC;
   m.attr("ROUTE_GEMM_G2") = (int)ROUTE_GEMM_G2;
   m.attr("ROUTE_HALO") = (int)ROUTE_HALO;
@@ -282,35 +249,28 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("g1s_gen_rows", &g1s_gen_rows);
   m.def("g1s_gen", [](uintptr_t X, uintptr_t Wt, uintptr_t Y, int NB, int GH, int GW, int N, int Kc, int ldw,
                       std::vector<std::array<int, 3>> taps, int H, int W, int OHo, int OWo, int OS, int ORY, int ORX,
-                      uintptr_t residual, uintptr_t stats, uintptr_t zero_ptr, int zero_n, std::array<uintptr_t, 4> bnb,
+                      uintptr_t residual, uintptr_t stats, uintptr_t zero_ptr, int zero_n, Ptr4 bnb,
                       int mode, uintptr_t stream) {
     g1s_gen(P<const bf16*>(X), P<const bf16*>(Wt), P<bf16*>(Y), NB, GH, GW, N, Kc, ldw, taps, H, W, OHo, OWo, OS, ORY,
             ORX, P<const bf16*>(residual), P<float*>(stats), P<float*>(zero_ptr), zero_n,
-            BnbArgs{P<const bf16*>(bnb[0]), P<const bf16*>(bnb[1]), P<const float*>(bnb[2]), P<const float*>(bnb[3])},
+            bnb_of(bnb),
             mode, S(stream));
   });
   m.def("g1s", [](uintptr_t X, uintptr_t Wt, uintptr_t Y, int M, int N, int K, int H, int W, int OH, int OW, int stride,
                   uintptr_t bias, uintptr_t residual, uintptr_t stats, int relu, uintptr_t zero_ptr, int zero_n,
-                  std::array<uintptr_t, 4> bnb, int mode, uintptr_t stream) {
+                  Ptr4 bnb, int mode, uintptr_t stream) {
     g1s(P<const bf16*>(X), P<const bf16*>(Wt), P<bf16*>(Y), M, N, K, H, W, OH, OW, stride, P<const float*>(bias),
         P<const bf16*>(residual), P<float*>(stats), relu, P<float*>(zero_ptr), zero_n,
-        BnbArgs{P<const bf16*>(bnb[0]), P<const bf16*>(bnb[1]), P<const float*>(bnb[2]), P<const float*>(bnb[3])},
+        bnb_of(bnb),
         mode, S(stream));
   });
   m.def("gemm_g2_row_tile", &gemm_g2_row_tile);
-  m.def("gemm_t2",
-        [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned a_bytes, unsigned b_bytes, int M,
-           int N, int Pn, int ldy, int Cs, int H, int W, int GH, int GW, int SY, int SX,
-           std::vector<std::array<int, 2>> taps, int splits, uintptr_t stream) {
-          T2Args a{};
-          a.dY = P<const bf16*>(dY); a.X = P<const bf16*>(X); a.slab = P<float*>(slab); a.bias_slab = P<float*>(bias_slab);
-          a.a_bytes = a_bytes; a.b_bytes = b_bytes; a.M = M; a.N = N; a.P = Pn; a.ldy = ldy; a.Cs = Cs;
-          a.H = H; a.W = W; a.GH = GH; a.GW = GW; a.SY = SY; a.SX = SX;
-          if (taps.size() > 64) throw std::runtime_error("gemm_t2: more than 64 taps");
-          a.ntaps = (int)taps.size();
-          for (size_t i = 0; i < taps.size(); ++i) { a.tap_dy[i] = taps[i][0]; a.tap_dx[i] = taps[i][1]; }
-          gemm_t2(a, splits, S(stream));
-        });
+  m.def("gemm_t2", &bind_gemm_t2);
+  // slab[split][M][N] = partial dY[P][M]^T . X[P][N]: one tap, a 1 x 1 grid per row
+  m.def("gemm_t2_plain", [](int f32, uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, unsigned a_bytes,
+                            unsigned b_bytes, int M, int N, int Pn, int splits, uintptr_t stream) {
+    bind_gemm_t2(f32, dY, X, slab, bias_slab, a_bytes, b_bytes, M, N, Pn, M, N, 1, 1, 1, 1, 1, 1, {{0, 0}}, splits, stream);
+  });
   m.def("gemm_t2_splits", &gemm_t2_splits);
   m.def("gemm_tn",
         [](uintptr_t dY, uintptr_t X, uintptr_t slab, uintptr_t bias_slab, int M, int N, int Pn, int mode, int nb,

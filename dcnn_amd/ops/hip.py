@@ -30,17 +30,66 @@ from .hip_layers import zero_
 from .hip_norm import *  # noqa: F401,F403
 
 
+# ---- tap tables: computed by the kernel library's shared host code (csrc/kernels/conv_args.cpp,
+# also used by the C++ host API), cached here per geometry so an eager launch builds no lists
 @functools.lru_cache(maxsize=1024)
 def _fwd_taps(C, W, KH, KW, ph, pw):
-    """Tap list of a forward conv: (dy, dx, src element offset, B-row element offset). Cached per
-    geometry (eager launches rebuild no Python lists); the tuple is never mutated."""
-    taps = []
-    for ky in range(KH):
-        for kx in range(KW):
-            dy, dx = ky - ph, kx - pw
-            taps.append((dy, dx, (dy * W + dx) * C, (ky * KW + kx) * C))
-    return tuple(taps)
+    """Tap list of a forward conv: (dy, dx, src element offset, B-row element offset); the tuple
+    is never mutated."""
+    return tuple(map(tuple, kernels().conv_fwd_taps(C, W, KH, KW, ph, pw)))
 
+
+@functools.lru_cache(maxsize=256)
+def _wgrad_taps(KH, KW, ph, pw):
+    """Tap list of a weight gradient: the (dy, dx) input offset of every kernel tap."""
+    return tuple(map(tuple, kernels().conv_wgrad_taps(KH, KW, ph, pw)))
+
+
+@functools.lru_cache(maxsize=1024)
+def _dgrad_classes(H, W, OW, Co, KH, KW, sh, sw, ph, pw):
+    """Stride-phase decomposition of a dgrad: ((ry, rx, GH, GW, taps) with taps, ...) and the
+    phases no tap reaches; taps = (dy offset, dx offset, dy element offset, B-row offset)."""
+    phases, taps = kernels().conv_dgrad_phases(H, W, OW, Co, KH, KW, sh, sw, ph, pw)
+    taps = tuple(map(tuple, taps))
+    cls = [(ry, rx, GH, GW, taps[t0:t0 + nt]) for ry, rx, GH, GW, t0, nt in phases]
+    return tuple(c for c in cls if c[4]), tuple(c for c in cls if not c[4])
+
+
+@functools.lru_cache(maxsize=1024)
+def _grouped(classes):
+    """Row classes of one grouped gemm_g2 launch: (flat tap list, (first tap, taps, ry, rx) per class)."""
+    taps_all, groups = [], []
+    for ry, rx, _, _, taps in classes:
+        groups.append((len(taps_all), len(taps), ry, rx))
+        taps_all += taps
+    return tuple(taps_all), tuple(groups)
+
+
+def _stats_ws(on, width, C, device, rows_fn, *shape):
+    """Workspace of a statistics epilogue -> (slab, rows, sums, zero_n): ``rows_fn(*shape)`` per-tile
+    rows of ``width`` x C partials and the [2][C] sums the kernel zeroes; all off without ``on``."""
+    if not on:
+        return None, 0, None, 0
+    rows = rows_fn(*shape)
+    return _empty((rows, width, C), F32, device), rows, _empty((2 * C,), F32, device), 2 * C
+
+
+def _with_bnb(dx, fuse, bnb, slab, rows, sums):
+    """dx, carrying the fused backward-BatchNorm statistics (``BnbRequest``) when ``fuse``."""
+    if fuse:
+        dx._bnb = (bnb.bn, slab, rows, sums)
+    return dx
+
+
+def _wgrad_split(K, splits, Co, Ng, grad_w, grad_b, device, st, launch, reduce=True):
+    """One split weight gradient: ``splits`` partial slabs [Co][Ng] (+ [Co] bias partials) written
+    by ``launch(slab ptr, bias slab ptr)``, then summed into grad_w / grad_b (+=)."""
+    slab = _empty((splits, Co, Ng), F32, device)
+    bslab = _empty((splits, Co), F32, device) if grad_b is not None else None
+    launch(slab.data_ptr(), ptr(bslab))
+    if reduce:
+        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
+    return slab, bslab
 
 
 # ---- split-precision fp32 convolutions on the bf16 halo kernels
@@ -177,40 +226,28 @@ def conv2d_fwd(x, w, bias, stride, pad, *, stats=False, residual=None, relu=Fals
         xs = act_split3(x)
         ws = split3_rows(w, Co * KH * KW, Ci, 1)
         y = _empty((N, Co, OH, OW), F32, x.device, True)
-        slab, rows, sums = None, 0, None
-        if stats:
-            rows = K.hconv_stat_rows(N, H, W, 3 * Ci, Co, KH * KW, 1)
-            slab = _empty((rows, 3, Co), F32, x.device)
-            sums = _empty((2 * Co,), F32, x.device)  # zeroed in-kernel
-        K.hconv(xs.data_ptr(), ws.data_ptr(), 0, _nbytes(xs), _nbytes(ws), N, H, W, 3 * Ci, Co, KH * KW * 3 * Ci,
-                [(t[0], t[1], t[3]) for t in _fwd_taps(3 * Ci, W, KH, KW, ph, pw)], ptr(bias), 0, ptr(slab),
-                int(relu), ptr(sums), 2 * Co if stats else 0, _NOBNB, y.data_ptr(), ptr(residual),
-                *_NOSPLIT, stream_ptr())
+        slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, K.hconv_stat_rows, N, H, W, 3 * Ci, Co, KH * KW, 1)
+        K.hconv(0, xs.data_ptr(), ws.data_ptr(), 0, _nbytes(xs), _nbytes(ws), N, H, W, 3 * Ci, Co, KH * KW * 3 * Ci,
+                _fwd_taps(3 * Ci, W, KH, KW, ph, pw), ptr(bias), 0, ptr(slab), int(relu), ptr(sums), zn, _NOBNB,
+                y.data_ptr(), ptr(residual), *_NOSPLIT, stream_ptr())
         return y, ((slab, rows, sums) if stats else None)
     if (x.dtype == F32 and _H3_F32 and (KH, KW, sh, sw, ph, pw) == (3, 3, 1, 1, 1, 1) and w.dim() == 4
             and w.shape[1] == Ci):
         # exact fp32 3x3 on the persistent halo conv (hconv3 F32 instances: v_mfma_f32_16x16x4_f32)
-        taps = [(t[0], t[1], t[3]) for t in _fwd_taps(Ci, W, KH, KW, ph, pw)]
-        if len(taps) == 9 and K.hconv3_f32_splits(N, H, W, Ci, Co, 9):
+        if K.hconv3_f32_splits(N, H, W, Ci, Co, 9):
             y = _empty((N, Co, OH, OW), F32, x.device, True)
-            rows = K.hconv_stat_rows(N, H, W, 2 * Ci, Co, 9, 0) if stats else 0
-            slab = _empty((rows, 3, Co), F32, x.device) if stats else None
-            sums = _empty((2 * Co,), F32, x.device) if stats else None  # zeroed in-kernel
-            if K.hconv3_f32(x.data_ptr(), w.data_ptr(), _nbytes(x), _nbytes(w), N, H, W, Ci, Co, KH * KW * Ci, taps,
-                            ptr(bias), ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, y.data_ptr(),
-                            ptr(residual), *_hconv_split(K, N, H, W, 2 * Ci, Co, 9, x.device), stream_ptr()):
+            slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, K.hconv_stat_rows, N, H, W, 2 * Ci, Co, 9, 0)
+            if K.hconv(1, x.data_ptr(), w.data_ptr(), 0, _nbytes(x), _nbytes(w), N, H, W, Ci, Co, KH * KW * Ci,
+                       _fwd_taps(Ci, W, KH, KW, ph, pw), ptr(bias), 0, ptr(slab), int(relu), ptr(sums), zn, _NOBNB,
+                       y.data_ptr(), ptr(residual), *_hconv_split(K, N, H, W, 2 * Ci, Co, 9, x.device), stream_ptr()):
                 _H3_F32_STATS["fwd"] += 1
                 return y, ((slab, rows, sums) if stats else None)
     if x.dtype == F32:  # fp32 compute path: MFMA f32 16x16x4 gathered GEMM
         y = _empty((N, Co, OH, OW), F32, x.device, True)
-        slab, rows, sums = None, 0, None
-        if stats:
-            rows = K.gemm_g2f_stat_rows(M, Co)
-            slab = _empty((rows, 3, Co), F32, x.device)
-            sums = _empty((2 * Co,), F32, x.device)  # zeroed in-kernel
-        K.gemm_g2f(x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), M, Co, Ci, H, W, OH, OW, sh, sw,
-                   _fwd_taps(Ci, W, KH, KW, ph, pw), KH * KW * Ci, Co, OH, OW, 1, 1, 0, 0, ptr(bias), ptr(residual),
-                   ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, _NOBNB, stream_ptr())
+        slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, K.gemm_g2f_stat_rows, M, Co)
+        K.gemm_g2(1, x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), M, Co, Ci, H, W, OH, OW, sh, sw,
+                  _fwd_taps(Ci, W, KH, KW, ph, pw), KH * KW * Ci, Co, OH, OW, 1, 1, 0, 0, ptr(bias), ptr(residual),
+                  ptr(slab), int(relu), ptr(sums), zn, _NOBNB, stream_ptr(), ())
         return y, ((slab, rows, sums) if stats else None)
     # the shared routing table (csrc/kernels/conv_route.cpp, also used by the C++ host API)
     g1s_mode = (1 if stats else 0) if (w.dim() == 4 and (not stats or (residual is None and not relu))) else -1
@@ -226,46 +263,31 @@ def conv2d_fwd(x, w, bias, stride, pad, *, stats=False, residual=None, relu=Fals
         rows = K.g1s_rows(M, Co, Ci, 1 if stats else 0)
         if rows:
             y = _empty((N, Co, OH, OW), BF16, x.device, True)
-            slab = _empty((rows, 3, Co), F32, x.device) if stats else None
-            sums = _empty((2 * Co,), F32, x.device) if stats else None  # zeroed in-kernel
+            slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, lambda: rows)
             K.g1s(x.data_ptr(), w.data_ptr(), y.data_ptr(), M, Co, Ci, H, W, OH, OW, sh, ptr(bias), ptr(residual),
-                  ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, _NOBNB, 1 if stats else 0, stream_ptr())
+                  ptr(slab), int(relu), ptr(sums), zn, _NOBNB, 1 if stats else 0, stream_ptr())
             return y, ((slab, rows, sums) if stats else None)
     taps = _fwd_taps(Ci, W, KH, KW, ph, pw)
     if route == K.ROUTE_HALO and len(taps) == KH * KW:
         y = _empty((N, Co, OH, OW), BF16, x.device, True)
-        slab, rows, sums = None, 0, None
-        if stats:
-            rows = K.hconv_stat_rows(N, H, W, Ci, Co, len(taps), 0)
-            slab = _empty((rows, 3, Co), F32, x.device)
-            sums = _empty((2 * Co,), F32, x.device)  # zeroed in-kernel
-        K.hconv(x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), N, H, W, Ci, Co, KH * KW * Ci,
-                [(t[0], t[1], t[3]) for t in taps], ptr(bias), ptr(residual), ptr(slab), int(relu), ptr(sums),
-                2 * Co if stats else 0, _NOBNB, 0, 0, *_hconv_split(K, N, H, W, Ci, Co, KH * KW, x.device),
-                stream_ptr())
+        slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, K.hconv_stat_rows, N, H, W, Ci, Co, len(taps), 0)
+        K.hconv(0, x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), N, H, W, Ci, Co, KH * KW * Ci,
+                taps, ptr(bias), ptr(residual), ptr(slab), int(relu), ptr(sums), zn, _NOBNB, 0, 0,
+                *_hconv_split(K, N, H, W, Ci, Co, KH * KW, x.device), stream_ptr())
         return y, ((slab, rows, sums) if stats else None)
     if route in (K.ROUTE_GEMM_G2, K.ROUTE_HALO, K.ROUTE_G1S):
         y = _empty((N, Co, OH, OW), BF16, x.device, True)
-        slab, rows, sums = None, 0, None
-        if stats:
-            rows = K.gemm_g2_stat_rows(M, Co)
-            slab = _empty((rows, 3, Co), F32, x.device)
-            sums = _empty((2 * Co,), F32, x.device)  # zeroed in-kernel
-        K.gemm_g2_grouped(x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), M, Co, Ci, H, W, OH, OW,
-                          sh, sw, _fwd_taps(Ci, W, KH, KW, ph, pw), KH * KW * Ci, Co, OH, OW, 1, 1, 0, 0, ptr(bias),
-                          ptr(residual), ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, _NOBNB,
-                          stream_ptr(), [])
+        slab, rows, sums, zn = _stats_ws(stats, 3, Co, x.device, K.gemm_g2_stat_rows, M, Co)
+        K.gemm_g2(0, x.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(x), _nbytes(w), M, Co, Ci, H, W, OH, OW, sh, sw,
+                  taps, KH * KW * Ci, Co, OH, OW, 1, 1, 0, 0, ptr(bias), ptr(residual), ptr(slab), int(relu),
+                  ptr(sums), zn, _NOBNB, stream_ptr(), ())
         return y, ((slab, rows, sums) if stats else None)
     # generic fallback (odd channel counts): v1 kernels
     y = _empty((N, Co, OH, OW), F32 if out_fp32 else BF16, x.device, True)
-    slab, rows = None, 0
-    if stats:
-        rows = K.gemm_nt_stat_rows(M, Co)
-        slab = _empty((rows, 3, Co), F32, x.device)
+    slab, rows, sums, _ = _stats_ws(stats, 3, Co, x.device, K.gemm_nt_stat_rows, M, Co)
     K.gemm_nt(x.data_ptr(), w.data_ptr(), y.data_ptr(), M, Co, KH * KW * Ci, 0, KH * KW * Ci, Co, CONV_FWD,
               N, H, W, Ci, OH, OW, KH, KW, sh, sw, ph, pw, ptr(bias), ptr(residual), ptr(slab),
               int(out_fp32), int(relu), stream_ptr())
-    sums = _empty((2 * Co,), F32, x.device) if stats else None
     return y, ((slab, rows, sums) if stats else None)
 
 
@@ -289,31 +311,6 @@ def set_conv_algo(name: str) -> None:
 def get_conv_algo() -> str:
     return _CONV_ALGO
 
-
-
-@functools.lru_cache(maxsize=1024)
-def _dgrad_classes(H, W, OW, Co, KH, KW, sh, sw, ph, pw):
-    """Stride-phase decomposition of a dgrad: ((ry, rx, GH, GW, taps) with taps, ...) and the
-    phases no tap reaches; taps = (dy offset, dx offset, dy element offset, B-row offset).
-    Cached per geometry (tuples, never mutated)."""
-    classes, empty = [], []
-    for ry in range(sh):
-        for rx in range(sw):
-            GH, GW = (H - ry + sh - 1) // sh, (W - rx + sw - 1) // sw
-            if GH <= 0 or GW <= 0:
-                continue
-            taps = []
-            for ky in range(KH):
-                if (ry + ph - ky) % sh:
-                    continue
-                dyo = (ry + ph - ky) // sh
-                for kx in range(KW):
-                    if (rx + pw - kx) % sw:
-                        continue
-                    dxo = (rx + pw - kx) // sw
-                    taps.append((dyo, dxo, (dyo * OW + dxo) * Co, (ky * KW + kx) * Co))
-            (classes if taps else empty).append((ry, rx, GH, GW, tuple(taps)))
-    return tuple(classes), tuple(empty)
 
 
 def conv2d_dgrad(dy, wt, x_shape, stride, pad, *, residual=None, bnb=None):
@@ -368,14 +365,11 @@ def conv2d_dgrad(dy, wt, x_shape, stride, pad, *, residual=None, bnb=None):
         # 18 / 20 / 30 us grouped vs 18 / 16 / 22 us filled on the ResNet-18 layers.)
         GH, GW = allc[0][2], allc[0][3]
         M = len(allc) * N * GH * GW
-        taps_all, groups = [], []
-        for ry, rx, _, _, taps in allc:
-            groups.append((len(taps_all), len(taps), ry, rx))
-            taps_all += taps
+        taps_all, groups = _grouped(allc)
         dx = _empty((N, Ci, H, W), BF16, dy.device, True)
-        K.gemm_g2_grouped(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), M, Ci, Co, OH, OW,
-                          GH, GW, 1, 1, taps_all, KH * KW * Co, Ci, H, W, sh, sw, 0, 0, 0, ptr(residual), 0, 0, 0, 0,
-                          _NOBNB, stream_ptr(), groups)
+        K.gemm_g2(0, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), M, Ci, Co, OH, OW, GH, GW,
+                  1, 1, taps_all, KH * KW * Co, Ci, H, W, sh, sw, 0, 0, 0, ptr(residual), 0, 0, 0, 0, _NOBNB,
+                  stream_ptr(), groups)
         return dx
     if empty_class:
         # positions no tap reaches keep the residual (or zero); a memset / async copy node, not a kernel
@@ -392,9 +386,9 @@ def conv2d_dgrad(dy, wt, x_shape, stride, pad, *, residual=None, bnb=None):
         # split-precision fp32 dgrad on the bf16 halo conv (see _F32_CONCAT)
         dys = act_split3(dy)
         wts = split3_rows(wt, Ci * KH * KW, Co, 1)
-        K.hconv(dys.data_ptr(), wts.data_ptr(), 0, _nbytes(dys), _nbytes(wts), N, OH, OW, 3 * Co, Ci,
-                KH * KW * 3 * Co, [(t[0], t[1], 3 * t[3]) for t in classes[0][4]], 0, 0, 0, 0, 0, 0, _NOBNB,
-                dx.data_ptr(), ptr(residual), *_NOSPLIT, st)
+        K.hconv(0, dys.data_ptr(), wts.data_ptr(), 0, _nbytes(dys), _nbytes(wts), N, OH, OW, 3 * Co, Ci,
+                KH * KW * 3 * Co, _dgrad_classes(H, W, OW, 3 * Co, KH, KW, sh, sw, ph, pw)[0][0][4], 0, 0, 0, 0, 0, 0,
+                _NOBNB, dx.data_ptr(), ptr(residual), *_NOSPLIT, st)
         return dx
     if (f32 and _H3_F32 and len(classes) == 1 and not empty_class and (KH, KW, sh, sw, ph, pw) == (3, 3, 1, 1, 1, 1)
             and len(classes[0][4]) == 9 and K.hconv3_f32_splits(N, OH, OW, Co, Ci, 9)):
@@ -402,82 +396,53 @@ def conv2d_dgrad(dy, wt, x_shape, stride, pad, *, residual=None, bnb=None):
         # with the consuming BatchNorm's ReLU mask + backward statistics in the epilogue when asked
         fuse32 = (bnb is not None and fusion.BNB and not bnb.pooled and bnb.x.dtype == F32
                   and tuple(bnb.x.shape) == (N, Ci, H, W) and (bnb.y is None or bnb.y.dtype == F32))
-        rows = K.hconv_stat_rows(N, H, W, 2 * Co, Ci, 9, 0) if fuse32 else 0
-        slab = _empty((rows, 2, Ci), F32, dy.device) if fuse32 else None
-        sums = _empty((2 * Ci,), F32, dy.device) if fuse32 else None  # zeroed in-kernel
-        if K.hconv3_f32(dy.data_ptr(), wt.data_ptr(), _nbytes(dy), _nbytes(wt), N, OH, OW, Co, Ci, KH * KW * Co,
-                        [(t[0], t[1], t[3]) for t in classes[0][4]], 0, ptr(slab), 0, ptr(sums),
-                        2 * Ci if fuse32 else 0, dx.data_ptr(), ptr(residual),
-                        *_hconv_split(K, N, OH, OW, 2 * Co, Ci, 9, dy.device), st,
-                        bnb.args() if fuse32 else _NOBNB):
+        slab, rows, sums, zn = _stats_ws(fuse32, 2, Ci, dy.device, K.hconv_stat_rows, N, H, W, 2 * Co, Ci, 9, 0)
+        if K.hconv(1, dy.data_ptr(), wt.data_ptr(), 0, _nbytes(dy), _nbytes(wt), N, OH, OW, Co, Ci, KH * KW * Co,
+                   classes[0][4], 0, 0, ptr(slab), 0, ptr(sums), zn, bnb.args() if fuse32 else _NOBNB, dx.data_ptr(),
+                   ptr(residual), *_hconv_split(K, N, OH, OW, 2 * Co, Ci, 9, dy.device), st):
             _H3_F32_STATS["dgrad"] += 1
-            if fuse32:
-                _H3_F32_STATS["dgrad_bnb"] += 1
-                dx._bnb = (bnb.bn, slab, rows, sums)
-            return dx
-    g2 = K.gemm_g2f if f32 else K.gemm_g2
+            _H3_F32_STATS["dgrad_bnb"] += int(fuse32)
+            return _with_bnb(dx, fuse32, bnb, slab, rows, sums)
     fuse = (bnb is not None and fusion.BNB and not bnb.pooled and not f32 and not empty_class and bnb.x.dtype == BF16
             and tuple(bnb.x.shape) == (N, Ci, H, W))
     if not f32 and len(classes) == 1 and not empty_class and route == K.ROUTE_HALO and \
             len(classes[0][4]) == KH * KW:
-        slab = sums = None
-        rows = 0
-        if fuse:
-            rows = K.hconv_stat_rows(N, H, W, Co, Ci, len(classes[0][4]), 0)
-            slab = _empty((rows, 2, Ci), F32, dy.device)
-            sums = _empty((2 * Ci,), F32, dy.device)  # zeroed in-kernel
-        K.hconv(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), N, OH, OW, Co, Ci, KH * KW * Co,
-                [(t[0], t[1], t[3]) for t in classes[0][4]], 0, ptr(residual), ptr(slab), 0, ptr(sums),
-                2 * Ci if fuse else 0, bnb.args() if fuse else _NOBNB, 0, 0,
-                *_hconv_split(K, N, OH, OW, Co, Ci, len(classes[0][4]), dy.device), st)
-        if fuse:
-            dx._bnb = (bnb.bn, slab, rows, sums)
-        return dx
+        slab, rows, sums, zn = _stats_ws(fuse, 2, Ci, dy.device, K.hconv_stat_rows, N, H, W, Co, Ci, KH * KW, 0)
+        K.hconv(0, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), N, OH, OW, Co, Ci,
+                KH * KW * Co, classes[0][4], 0, ptr(residual), ptr(slab), 0, ptr(sums), zn,
+                bnb.args() if fuse else _NOBNB, 0, 0, *_hconv_split(K, N, OH, OW, Co, Ci, KH * KW, dy.device), st)
+        return _with_bnb(dx, fuse, bnb, slab, rows, sums)
     if (not f32 and fusion.G2_GROUP and len(classes) > 1 and len({(c[2], c[3]) for c in classes}) == 1
             and (N * classes[0][2] * classes[0][3]) % 128 == 0):
         # all stride phases in ONE grouped launch (gemm_g2 row classes): no per-phase launch
         # boundaries, and the grid covers the whole dgrad instead of a quarter of it
         GH, GW = classes[0][2], classes[0][3]
         M = len(classes) * N * GH * GW
-        taps_all, groups = [], []
-        for ry, rx, _, _, taps in classes:
-            groups.append((len(taps_all), len(taps), ry, rx))
-            taps_all += taps
-        rows = K.gemm_g2_stat_rows(M, Ci) if fuse else 0
-        slab = _empty((rows, 2, Ci), F32, dy.device) if fuse else None
-        sums = _empty((2 * Ci,), F32, dy.device) if fuse else None
-        K.gemm_g2_grouped(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), M, Ci, Co, OH, OW,
-                          GH, GW, 1, 1, taps_all, KH * KW * Co, Ci, H, W, sh, sw, 0, 0, 0, ptr(residual), ptr(slab), 0,
-                          ptr(sums), 2 * Ci if fuse else 0, bnb.args() if fuse else _NOBNB, st, groups)
-        if fuse:
-            dx._bnb = (bnb.bn, slab, rows, sums)
-        return dx
+        taps_all, groups = _grouped(classes)
+        slab, rows, sums, zn = _stats_ws(fuse, 2, Ci, dy.device, K.gemm_g2_stat_rows, M, Ci)
+        K.gemm_g2(0, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), M, Ci, Co, OH, OW, GH, GW,
+                  1, 1, taps_all, KH * KW * Co, Ci, H, W, sh, sw, 0, 0, 0, ptr(residual), ptr(slab), 0, ptr(sums), zn,
+                  bnb.args() if fuse else _NOBNB, st, groups)
+        return _with_bnb(dx, fuse, bnb, slab, rows, sums)
     if not f32 and route == K.ROUTE_G1S and not empty_class and len(classes) == 1:
         # streaming 1x1 data gradient (g1s.hip), backward-BatchNorm fusion in its epilogue
         rows = K.g1s_rows(N * H * W, Ci, Co, 2 if fuse else 0)
         if rows:
-            slab = _empty((rows, 2, Ci), F32, dy.device) if fuse else None
-            sums = _empty((2 * Ci,), F32, dy.device) if fuse else None
+            slab, rows, sums, zn = _stats_ws(fuse, 2, Ci, dy.device, lambda: rows)
             K.g1s(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), N * H * W, Ci, Co, H, W, H, W, 1, 0, ptr(residual),
-                  ptr(slab), 0, ptr(sums), 2 * Ci if fuse else 0, bnb.args() if fuse else _NOBNB, 2 if fuse else 0, st)
-            if fuse:
-                dx._bnb = (bnb.bn, slab, rows, sums)
-            return dx
+                  ptr(slab), 0, ptr(sums), zn, bnb.args() if fuse else _NOBNB, 2 if fuse else 0, st)
+            return _with_bnb(dx, fuse, bnb, slab, rows, sums)
     crow = [K.gemm_g2_stat_rows(N * GH * GW, Ci) if fuse else 0 for _, _, GH, GW, _ in classes]
-    rows = sum(crow)
-    slab = _empty((rows, 2, Ci), F32, dy.device) if fuse else None
-    sums = _empty((2 * Ci,), F32, dy.device) if fuse else None
+    slab, rows, sums, _ = _stats_ws(fuse, 2, Ci, dy.device, sum, crow)
     r0 = 0
     for k, (ry, rx, GH, GW, taps) in enumerate(classes):
         sp = slab.data_ptr() + r0 * 2 * Ci * 4 if fuse else 0
         zp = ptr(sums) if (fuse and k == 0) else 0
-        g2(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), N * GH * GW, Ci, Co, OH, OW,
-           GH, GW, 1, 1, taps, KH * KW * Co, Ci, H, W, sh, sw, ry, rx, 0, ptr(residual), sp, 0, zp,
-           2 * Ci if zp else 0, bnb.args() if fuse else _NOBNB, st)
+        K.gemm_g2(int(f32), dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), _nbytes(dy), _nbytes(wt), N * GH * GW, Ci, Co,
+                  OH, OW, GH, GW, 1, 1, taps, KH * KW * Co, Ci, H, W, sh, sw, ry, rx, 0, ptr(residual), sp, 0, zp,
+                  2 * Ci if zp else 0, bnb.args() if fuse else _NOBNB, st, ())
         r0 += crow[k]
-    if fuse:
-        dx._bnb = (bnb.bn, slab, rows, sums)
-    return dx
+    return _with_bnb(dx, fuse, bnb, slab, rows, sums)
 
 
 def conv2d_wgrad(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
@@ -493,7 +458,8 @@ def conv2d_wgrad(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
     OH, OW = dy.shape[2], dy.shape[3]
     P = N * OH * OW
     st = stream_ptr()
-    taps = [(ky - pad[0], kx - pad[1]) for ky in range(KH) for kx in range(KW)]
+    dev = x.device
+    taps = _wgrad_taps(KH, KW, pad[0], pad[1])
     hw_ok = (Cx == Ci and tuple(stride) == (1, 1) and (OH, OW) == (H, W)
              and 1 < len(taps) <= 9 and all(abs(a) <= 1 and abs(b) <= 1 for a, b in taps)
              and K.hwgrad_supported(N, H, W, Ci, Co, len(taps)))
@@ -501,36 +467,27 @@ def conv2d_wgrad(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
         # split-precision fp32 on the halo wgrad: three (dY, X) channel windows of the split rows
         # (dyh, xh), (dyh, xl), (dyl, xh); the bias partial is sum(dyh) + sum(dyl)
         dys, xs = act_split3(dy), act_split3(x)
-        Ng = KH * KW * Ci
         splits = K.hwgrad_splits(N, H, W, Ci, Co)
-        slab = _empty((3 * splits, Co, Ng), F32, x.device)
-        bslab = _empty((3 * splits, Co), F32, x.device) if grad_b is not None else None
-        K.hwgrad(dys.data_ptr(), xs.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dys), _nbytes(xs), N, H, W, Ci,
-                 Co, taps, splits, 3 * Co, 3 * Ci, [(0, 0, 1), (0, Ci, 0), (Co, 0, 1)], st)
-        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, 3 * splits, st)
+        _wgrad_split(K, 3 * splits, Co, KH * KW * Ci, grad_w, grad_b, dev, st, lambda slab, bslab: K.hwgrad(
+            0, dys.data_ptr(), xs.data_ptr(), slab, bslab, _nbytes(dys), _nbytes(xs), N, H, W, Ci, Co, taps, splits,
+            3 * Co, 3 * Ci, ((0, 0, 1), (0, Ci, 0), (Co, 0, 1)), st))
         return
     if (dy.dtype == F32 and _HW_F32 and Cx == Ci and (KH, KW, *stride, *pad) == (3, 3, 1, 1, 1, 1)
             and (OH, OW) == (H, W) and K.hwgrad_f32_supported(N, H, W, Ci, Co)):
-        Ng = 9 * Ci
         splits = K.hwgrad_f32_splits(N, H, W, Ci, Co)
-        slab = _empty((splits, Co, Ng), F32, x.device)
-        bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        K.hwgrad_f32(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(x), N, H, W,
-                     Ci, Co, splits, st)
+        _wgrad_split(K, splits, Co, 9 * Ci, grad_w, grad_b, dev, st, lambda slab, bslab: K.hwgrad(
+            2, dy.data_ptr(), x.data_ptr(), slab, bslab, _nbytes(dy), _nbytes(x), N, H, W, Ci, Co, taps, splits, 0, 0,
+            (), st))
         _H3_F32_STATS["wgrad"] += 1
-        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
         return
     if dy.dtype == F32:
         assert x.dtype == F32 and Cx == Ci
+        assert grad_w.is_contiguous(memory_format=CL) or KH * KW == 1 or Ci == 1
         Ng = KH * KW * Ci
         splits = K.gemm_t2f_splits(Co, Ng, P)
-        slab = _empty((splits, Co, Ng), F32, x.device)
-        bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        taps = [(ky - pad[0], kx - pad[1]) for ky in range(KH) for kx in range(KW)]
-        K.gemm_t2f(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), Co, Ng, P, Co, Ci, H, W, OH, OW,
-                   stride[0], stride[1], taps, splits, st)
-        assert grad_w.is_contiguous(memory_format=CL) or KH * KW == 1 or Ci == 1
-        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
+        _wgrad_split(K, splits, Co, Ng, grad_w, grad_b, dev, st, lambda slab, bslab: K.gemm_t2(
+            1, dy.data_ptr(), x.data_ptr(), slab, bslab, 0, 0, Co, Ng, P, Co, Ci, H, W, OH, OW, stride[0], stride[1],
+            taps, splits, st))
         return
     # the shared routing table (csrc/kernels/conv_route.cpp, also used by the C++ host API)
     route = (K.conv_wgrad_route(N, Ci, H, W, Co, KH, KW, stride[0], stride[1], pad[0], pad[1], OH, OW, -1)
@@ -539,36 +496,28 @@ def conv2d_wgrad(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
          bias=grad_b is not None, route=int(route))
     if route == K.ROUTE_HALO_S2 and fusion.HWGRAD_S2:
         # stride-2 halo wgrad: the 64-pixel tile's (2 TH + 1) x (2 TW + 1) input halo staged once for 9 taps
-        Ng = 9 * Ci
         splits = K.hwgrad_s2_splits(N, OH, OW, Ci, Co)
-        slab = _empty((splits, Co, Ng), F32, x.device)
-        bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        K.hwgrad_s2(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(x), N, OH, OW, Ci,
-                    Co, splits, st)
-        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
+        _wgrad_split(K, splits, Co, 9 * Ci, grad_w, grad_b, dev, st, lambda slab, bslab: K.hwgrad(
+            1, dy.data_ptr(), x.data_ptr(), slab, bslab, _nbytes(dy), _nbytes(x), N, OH, OW, Ci, Co, (), splits, 0, 0,
+            (), st))
         return
     if route == K.ROUTE_HALO:
         # halo-tiled wgrad: X read ~1.4x instead of once per tap
-        Ng = KH * KW * Ci
         splits = K.hwgrad_splits(N, H, W, Ci, Co)
-        slab = _empty((splits, Co, Ng), F32, x.device)
-        bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        K.hwgrad(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(x), N, H, W, Ci, Co,
-                 taps, splits, Co, Ci, [], st)
-        _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
+        _wgrad_split(K, splits, Co, KH * KW * Ci, grad_w, grad_b, dev, st, lambda slab, bslab: K.hwgrad(
+            0, dy.data_ptr(), x.data_ptr(), slab, bslab, _nbytes(dy), _nbytes(x), N, H, W, Ci, Co, taps, splits, Co, Ci,
+            (), st))
         return
     if _g2_ok(Cx, Co) and P < (1 << 24):
         Ng = KH * KW * Cx
         splits = K.gemm_t2_splits(Co, Ng, P)
-        slab = _empty((splits, Co, Ng), F32, x.device)
-        bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        taps = [(ky - pad[0], kx - pad[1]) for ky in range(KH) for kx in range(KW)]
-        K.gemm_t2(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(x), Co, Ng, P, Co, Cx,
-                  H, W, OH, OW, stride[0], stride[1], taps, splits, st)
+        slab, bslab = _wgrad_split(K, splits, Co, Ng, grad_w, grad_b, dev, st, lambda slab, bslab: K.gemm_t2(
+            0, dy.data_ptr(), x.data_ptr(), slab, bslab, _nbytes(dy), _nbytes(x), Co, Ng, P, Co, Cx, H, W, OH, OW,
+            stride[0], stride[1], taps, splits, st), reduce=Cx == Ci)
         if Cx == Ci:
-            _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
             return
-        tmp = _empty((Co, KH, KW, Cx), F32, x.device)
+        # zero-padded input channels (RGB stem): reduce to a temporary, keep the first Ci columns
+        tmp = _empty((Co, KH, KW, Cx), F32, dev)
         K.splitk_reduce(slab.data_ptr(), tmp.data_ptr(), Co * Ng, splits, 0, st)
         if grad_w.is_contiguous(memory_format=CL):
             K.rows_copy(1, tmp.data_ptr(), Cx, grad_w.data_ptr(), Ci, Co * KH * KW, Ci, st)
@@ -577,11 +526,9 @@ def conv2d_wgrad(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
         if grad_b is not None:
             K.splitk_reduce(bslab.data_ptr(), grad_b.data_ptr(), Co, splits, 1, st)
         return
+    assert grad_w.is_contiguous(memory_format=CL) or KH * KW == 1 or Ci == 1
     Ng = KH * KW * Ci
     splits = K.gemm_tn_splits(Co, Ng, P)
-    slab = _empty((splits, Co, Ng), F32, x.device)
-    bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-    K.gemm_tn(dy.data_ptr(), x.data_ptr(), slab.data_ptr(), ptr(bslab), Co, Ng, P, CONV_FWD,
-              N, H, W, Ci, OH, OW, KH, KW, stride[0], stride[1], pad[0], pad[1], 0, splits, st)
-    assert grad_w.is_contiguous(memory_format=CL) or KH * KW == 1 or Ci == 1
-    _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)
+    _wgrad_split(K, splits, Co, Ng, grad_w, grad_b, dev, st, lambda slab, bslab: K.gemm_tn(
+        dy.data_ptr(), x.data_ptr(), slab, bslab, Co, Ng, P, CONV_FWD, N, H, W, Ci, OH, OW, KH, KW, stride[0],
+        stride[1], pad[0], pad[1], 0, splits, st))

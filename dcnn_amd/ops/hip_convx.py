@@ -5,7 +5,7 @@ from __future__ import annotations
 
 from ..runtime import arena as _arena
 from ._ext import dt_code, kernels, ptr, stream_ptr
-from .hip_base import (BF16, CL, F32, _NOBNB, _check_act, _empty, _nbytes, _rec, _reduce_wb,
+from .hip_base import (BF16, CL, F32, _check_act, _empty, _nbytes, _rec, _reduce_wb,
                        conv_out_hw)
 
 
@@ -154,10 +154,8 @@ def conv2d_fwd_im2col(x, w, bias, stride, pad, *, stats=False, residual=None, re
         rows = (K.gemm_g2f_stat_rows if f32 else K.gemm_g2_stat_rows)(M, Co)
         slab = _empty((rows, 3, Co), F32, x.device)
         sums = _empty((2 * Co,), F32, x.device)  # zeroed in-kernel
-    (K.gemm_g2f if f32 else K.gemm_g2)(col.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(col), _nbytes(w), M, Co,
-                                       Kc, 1, 1, 1, 1, 1, 1, [(0, 0, 0, 0)], Kc, Co, 1, 1, 1, 1, 0, 0, ptr(bias),
-                                       ptr(residual), ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, _NOBNB,
-                                       stream_ptr())
+    K.gemm_g2_plain(int(f32), col.data_ptr(), w.data_ptr(), y.data_ptr(), _nbytes(col), _nbytes(w), M, Co, Kc, ptr(bias),
+                    ptr(residual), ptr(slab), int(relu), ptr(sums), 2 * Co if stats else 0, stream_ptr())
     return y, ((slab, rows, sums) if stats else None)
 
 
@@ -171,9 +169,8 @@ def conv2d_dgrad_im2col(dy, wt, x_shape, stride, pad, *, residual=None):
     M = dy.shape[0] * dy.shape[2] * dy.shape[3]
     Nc = Ci * KH * KW
     colg = _empty((M, Nc), dy.dtype, dy.device)
-    (K.gemm_g2f if dy.dtype == F32 else K.gemm_g2)(dy.data_ptr(), wt.data_ptr(), colg.data_ptr(), _nbytes(dy),
-                                                   _nbytes(wt), M, Nc, Co, 1, 1, 1, 1, 1, 1, [(0, 0, 0, 0)], Co, Nc,
-                                                   1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, _NOBNB, stream_ptr())
+    K.gemm_g2_plain(int(dy.dtype == F32), dy.data_ptr(), wt.data_ptr(), colg.data_ptr(), _nbytes(dy), _nbytes(wt), M, Nc,
+                    Co, 0, 0, 0, 0, 0, 0, stream_ptr())
     return col2im_nhwc(colg, x_shape, KH, KW, stride, pad, residual=residual, chan_major=True)
 
 
@@ -190,12 +187,11 @@ def conv2d_wgrad_im2col(dy, x, w_shape, stride, pad, grad_w, grad_b=None):
         splits = K.gemm_t2f_splits(Co, Ng, P)
         slab = _empty((splits, Co, Ng), F32, x.device)
         bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        K.gemm_t2f(dy.data_ptr(), col.data_ptr(), slab.data_ptr(), ptr(bslab), Co, Ng, P, Co, Ng, 1, 1, 1, 1, 1, 1,
-                   [(0, 0)], splits, st)
+        K.gemm_t2_plain(1, dy.data_ptr(), col.data_ptr(), slab.data_ptr(), ptr(bslab), 0, 0, Co, Ng, P, splits, st)
     else:
         splits = K.gemm_t2_splits(Co, Ng, P)
         slab = _empty((splits, Co, Ng), F32, x.device)
         bslab = _empty((splits, Co), F32, x.device) if grad_b is not None else None
-        K.gemm_t2(dy.data_ptr(), col.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(col), Co, Ng, P,
-                  Co, Ng, 1, 1, 1, 1, 1, 1, [(0, 0)], splits, st)
+        K.gemm_t2_plain(0, dy.data_ptr(), col.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy), _nbytes(col), Co, Ng,
+                        P, splits, st)
     _reduce_wb(K, slab, grad_w, Co * Ng, bslab, grad_b, Co, splits, st)

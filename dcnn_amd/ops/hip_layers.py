@@ -6,7 +6,7 @@ import torch
 from ..runtime import arena as _arena
 from . import fusion
 from ._ext import dt_code, kernels, ptr, stream_ptr
-from .hip_base import (BF16, CL, F32, PLAIN, _NOBNB, _check_act, _empty, _empty_like, _g2_ok, _nbytes,
+from .hip_base import (BF16, CL, F32, PLAIN, _check_act, _empty, _empty_like, _g2_ok, _nbytes,
                        _reduce_wb, _ticket, conv_out_hw, pool_out_hw)
 
 
@@ -16,15 +16,13 @@ def dense_fwd(x2d, w2d, bias):
     Out = w2d.shape[0]
     if x2d.dtype == F32:
         y = _empty((N, Out), F32, x2d.device)
-        kernels().gemm_g2f(x2d.data_ptr(), w2d.data_ptr(), y.data_ptr(), _nbytes(x2d), _nbytes(w2d), N, Out, In, 1, 1,
-                           1, 1, 1, 1, [(0, 0, 0, 0)], In, Out, 1, 1, 1, 1, 0, 0, ptr(bias), 0, 0, 0, 0, 0, _NOBNB,
-                           stream_ptr())
+        kernels().gemm_g2_plain(1, x2d.data_ptr(), w2d.data_ptr(), y.data_ptr(), _nbytes(x2d), _nbytes(w2d), N, Out, In,
+                                ptr(bias), 0, 0, 0, 0, 0, stream_ptr())
         return y
     y = _empty((N, Out), BF16, x2d.device)
     if _g2_ok(In, Out):
-        kernels().gemm_g2(x2d.data_ptr(), w2d.data_ptr(), y.data_ptr(), _nbytes(x2d), _nbytes(w2d), N, Out, In, 1, 1,
-                          1, 1, 1, 1, [(0, 0, 0, 0)], In, Out, 1, 1, 1, 1, 0, 0, ptr(bias), 0, 0, 0, 0, 0, _NOBNB,
-                          stream_ptr())
+        kernels().gemm_g2_plain(0, x2d.data_ptr(), w2d.data_ptr(), y.data_ptr(), _nbytes(x2d), _nbytes(w2d), N, Out, In,
+                                ptr(bias), 0, 0, 0, 0, 0, stream_ptr())
         return y
     kernels().gemm_nt(x2d.data_ptr(), w2d.data_ptr(), y.data_ptr(), N, Out, In, In, In, Out, PLAIN,
                       0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 0, 0, ptr(bias), 0, 0, 0, 0, stream_ptr())
@@ -37,15 +35,13 @@ def dense_dgrad(dy2d, wt2d):
     In = wt2d.shape[0]
     if dy2d.dtype == F32:
         dx = _empty((N, In), F32, dy2d.device)
-        kernels().gemm_g2f(dy2d.data_ptr(), wt2d.data_ptr(), dx.data_ptr(), _nbytes(dy2d), _nbytes(wt2d), N, In, Out,
-                           1, 1, 1, 1, 1, 1, [(0, 0, 0, 0)], Out, In, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, _NOBNB,
-                           stream_ptr())
+        kernels().gemm_g2_plain(1, dy2d.data_ptr(), wt2d.data_ptr(), dx.data_ptr(), _nbytes(dy2d), _nbytes(wt2d), N, In,
+                                Out, 0, 0, 0, 0, 0, 0, stream_ptr())
         return dx
     dx = _empty((N, In), BF16, dy2d.device)
     if _g2_ok(Out, In):
-        kernels().gemm_g2(dy2d.data_ptr(), wt2d.data_ptr(), dx.data_ptr(), _nbytes(dy2d), _nbytes(wt2d), N, In, Out, 1,
-                          1, 1, 1, 1, 1, [(0, 0, 0, 0)], Out, In, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, _NOBNB,
-                          stream_ptr())
+        kernels().gemm_g2_plain(0, dy2d.data_ptr(), wt2d.data_ptr(), dx.data_ptr(), _nbytes(dy2d), _nbytes(wt2d), N, In,
+                                Out, 0, 0, 0, 0, 0, 0, stream_ptr())
         return dx
     kernels().gemm_nt(dy2d.data_ptr(), wt2d.data_ptr(), dx.data_ptr(), N, In, Out, Out, Out, In, PLAIN,
                       0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, stream_ptr())
@@ -61,14 +57,13 @@ def dense_wgrad(dy2d, x2d, grad_w, grad_b=None):
         splits = K.gemm_t2f_splits(Out, In, N)
         slab = _empty((splits, Out, In), F32, x2d.device)
         bslab = _empty((splits, Out), F32, x2d.device) if grad_b is not None else None
-        K.gemm_t2f(dy2d.data_ptr(), x2d.data_ptr(), slab.data_ptr(), ptr(bslab), Out, In, N, Out, In, 1, 1, 1, 1,
-                   1, 1, [(0, 0)], splits, st)
+        K.gemm_t2_plain(1, dy2d.data_ptr(), x2d.data_ptr(), slab.data_ptr(), ptr(bslab), 0, 0, Out, In, N, splits, st)
     elif _g2_ok(In, Out):
         splits = K.gemm_t2_splits(Out, In, N)
         slab = _empty((splits, Out, In), F32, x2d.device)
         bslab = _empty((splits, Out), F32, x2d.device) if grad_b is not None else None
-        K.gemm_t2(dy2d.data_ptr(), x2d.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy2d), _nbytes(x2d), Out, In,
-                  N, Out, In, 1, 1, 1, 1, 1, 1, [(0, 0)], splits, st)
+        K.gemm_t2_plain(0, dy2d.data_ptr(), x2d.data_ptr(), slab.data_ptr(), ptr(bslab), _nbytes(dy2d), _nbytes(x2d),
+                        Out, In, N, splits, st)
     else:
         splits = K.gemm_tn_splits(Out, In, N)
         slab = _empty((splits, Out, In), F32, x2d.device)

@@ -45,6 +45,8 @@ CONV_CASES = [
     (2, 256, 8, 8, 256, 1, 1, 0),
     (4, 32, 32, 32, 64, 3, 1, 1),   # dgrad: 32 output channels on the halo conv (half-filled tile)
     (2, 64, 16, 16, 32, 3, 1, 1),   # forward: 32 output channels on the halo conv
+    (2, 64, 9, 7, 128, 3, 2, 1),    # dgrad: non-uniform stride phases (one launch per phase)
+    (2, 32, 8, 8, 64, 2, 2, 0),     # dgrad: one tap per phase, 32 rows per phase (not a multiple of 128)
 ]
 
 
