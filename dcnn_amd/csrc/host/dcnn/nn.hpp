@@ -228,10 +228,23 @@ class Dense : public Layer {
   Tensor forward(const Tensor& x, bool training) override;
   Tensor backward(const Tensor& dy) override;
   double flops(const std::vector<int64_t>& in) const override { return 6.0 * in[0] * in_ * out_; }
+  // GPU classifier head (average pool -> flatten -> dense closing a sequence; fuse_bn_relu wires
+  // it): the pool's training forward runs gpu_ops::head_fwd, pool + this layer in one kernel, and
+  // hands the pooled tile (this layer's cached input) and the logits over (run_head); forward then
+  // returns those logits, and backward runs gpu_ops::head_bwd and returns the pool's input
+  // gradient, which the flatten and the pool recognise and pass through (is_head_dx). Each
+  // hand-over is by tensor identity, so a layer driven on its own (a teacher-forced segment)
+  // runs its own kernels.
+  void set_head_pool(class Pool2D* p) { head_pool_ = p; }
+  // false: geometry outside gpu_ops::head_supported (the pool runs its own kernel)
+  bool run_head(const Tensor& x, const PoolShape& p, Tensor& pooled);
+  // dy is the pool's input gradient this layer's backward just computed; take: the last consumer
+  bool is_head_dx(const Tensor& dy, bool take);
 
  private:
   int in_, out_;
   bool bias_;
+  class Pool2D* head_pool_ = nullptr;
 };
 
 class BatchNorm : public Layer {
@@ -379,9 +392,12 @@ class Pool2D : public Layer {
   // the index buffer for a pre-pooled output `ypool` of an input of shape `in`
   uint8_t* accept_prepooled(const Tensor& ypool, const std::vector<int64_t>& in);
   void clear_prepooled() { mbc().flag = false; }
+  // GPU: this average pool opens the classifier head that `d` closes (Dense::set_head_pool)
+  void set_head_dense(class Dense* d) { head_ = d; }
 
  private:
   class BatchNorm* bn_ = nullptr;
+  class Dense* head_ = nullptr;
   bool max_;
   int kh_, kw_, sh_, sw_, ph_, pw_;
 };
@@ -394,6 +410,11 @@ class Flatten : public Layer {
   std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override;
   Tensor forward(const Tensor& x, bool training) override;
   Tensor backward(const Tensor& dy) override;
+  // GPU: between the pool and the dense layer of a fused classifier head (Dense::set_head_pool)
+  void set_head_dense(class Dense* d) { head_ = d; }
+
+ private:
+  class Dense* head_ = nullptr;
 };
 
 // out = act(F(x) + S(x)): F the main path, S the projection shortcut (identity when empty).

@@ -148,6 +148,14 @@ void stem_wgrad_bn(const void* dy, const float* x, float* gw, float* gb, const C
 void dense_fwd(const void* x, const void* w, const float* bias, void* y, int N, int In, int Out);
 void dense_dgrad(const void* dy, const void* w, void* dx, int N, int In, int Out);
 void dense_wgrad(const void* dy, const void* x, float* gw, float* gb, int N, int In, int Out);
+// the classifier head fused (csrc/kernels/head.hip): p the whole-map average pool, w the dense
+// layer's bf16 [Out][p.C]. head_fwd: x -> pooled [N][C] and the logits y [N][Out]; head_bwd: the
+// dense layer's weight / bias gradient (+= through the split reduce, as dense_wgrad) and, with dx
+// set, the pool's input gradient
+bool head_supported(const PoolShape& p, int Out);
+void head_fwd(const void* x, const void* w, const float* bias, void* pooled, void* y, const PoolShape& p, int Out);
+void head_bwd(const void* dy, const void* w, const void* pooled, void* dx, float* gw, float* gb, const PoolShape& p,
+              int Out);
 // training: batch statistics (saved mean / istd, running stats updated); eval: running stats
 // relu: y = max(bn(x) [+ residual], 0) in the same pass (a BatchNorm followed by a ReLU, or the
 // tail BatchNorm of a residual block with the shortcut added)

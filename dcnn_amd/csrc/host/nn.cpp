@@ -414,8 +414,53 @@ void Dense::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
   if (bias_) add_param("bias", {out_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)out_, bound, seed + 1));
 }
 
+// (DCNN_HEAD_FUSE=0: the classifier head as its six separate kernels — test / A-B hook)
+static bool head_fuse_enabled() {
+  static const bool on = [] {
+    const char* v = std::getenv("DCNN_HEAD_FUSE");
+    return !(v && std::string(v) == "0");
+  }();
+  return on;
+}
+
+bool Dense::run_head(const Tensor& x, const PoolShape& p, Tensor& pooled) {
+  MbCache& mc = mbc();
+  mc.flag = false;
+  if (!dev_.is_gpu() || !head_fuse_enabled() || p.C != in_ || !gpu_ops::head_supported(p, out_)) return false;
+  pooled = act_empty({p.N, p.C, 1, 1}, dev_);
+  Tensor y = act_empty({p.N, out_, 1, 1}, dev_);
+  const float* b = bias_ ? params_[1].value.ptr<float>() : nullptr;
+  gpu_ops::head_fwd(x.data(), params_[0].shadow.data(), b, pooled.data(), y.data(), p, out_);
+  mc.a = pooled;  // (this layer's input)
+  mc.b = y;       // (handed out by forward)
+  mc.shape = x.shape();
+  mc.flag = true;
+  return true;
+}
+
+bool Dense::is_head_dx(const Tensor& dy, bool take) {
+  MbCache& mc = mbc();
+  if (head_pool_ == nullptr || mc.u == 0) return false;
+  // (without an input gradient, Dense::backward hands an undefined tensor down)
+  const bool same = mc.c.defined() ? dy.defined() && dy.data() == mc.c.data() : !dy.defined();
+  if (same && take) {
+    mc.c = Tensor();
+    mc.u = 0;
+  }
+  return same;
+}
+
 Tensor Dense::forward(const Tensor& x, bool training) {
   (void)training;
+  mbc().c = Tensor();
+  mbc().u = 0;
+  if (mbc().flag && mbc().b.defined() && x.data() == mbc().a.data()) {
+    Tensor y = mbc().b;  // computed with the pool (run_head)
+    mbc().b = Tensor();
+    return y;
+  }
+  mbc().flag = false;  // (driven on its own, or the pool ran its own kernel)
+  mbc().b = Tensor();
   Tensor& x_ = mbc().a;
   check_act(x, dev_, "dense");
   const int N = (int)x.dim(0);
@@ -434,6 +479,17 @@ Tensor Dense::backward(const Tensor& dy) {
   const Tensor& x_ = mbc().a;
   const int N = (int)x_.dim(0);
   float* gb = bias_ ? params_[1].grad.ptr<float>() : nullptr;
+  if (head_pool_ != nullptr && mbc().flag) {
+    // weight / bias gradient and the pool's input gradient in one kernel (the flatten and the
+    // pool pass it through)
+    const PoolShape p = head_pool_->shape_for(mbc().shape);
+    Tensor dx = input_grad_ ? act_empty(mbc().shape, dev_) : Tensor();
+    gpu_ops::head_bwd(dy.data(), params_[0].shadow.data(), x_.data(), input_grad_ ? dx.data() : nullptr,
+                      params_[0].grad.ptr<float>(), gb, p, out_);
+    mbc().c = dx;
+    mbc().u = 1;  // (handed out)
+    return dx;
+  }
   if (dev_.is_gpu()) {
     gpu_ops::dense_wgrad(dy.data(), x_.data(), params_[0].grad.ptr<float>(), gb, N, in_, out_);
     if (!input_grad_) return Tensor();
@@ -746,7 +802,9 @@ static int fuse_kind(const Layer* l) {
   if (dynamic_cast<const Conv2D*>(l)) return FK_CONV;
   if (dynamic_cast<const BatchNorm*>(l)) return FK_BN;
   if (auto* a = dynamic_cast<const Activation*>(l)) return a->is_relu() ? FK_RELU : FK_ACT;
-  if (auto* p = dynamic_cast<const Pool2D*>(l)) return p->is_max() ? FK_MAXPOOL : FK_OTHER;
+  if (auto* p = dynamic_cast<const Pool2D*>(l)) return p->is_max() ? FK_MAXPOOL : FK_AVGPOOL;
+  if (dynamic_cast<const Flatten*>(l)) return FK_FLATTEN;
+  if (dynamic_cast<const Dense*>(l)) return FK_DENSE;
   return FK_OTHER;
 }
 
@@ -780,6 +838,12 @@ void fuse_bn_relu(std::vector<std::unique_ptr<Layer>>& seq, bool on) {
       act->set_passthrough(on && (f[i] & FF_PASSTHROUGH));
     } else if (auto* pool = dynamic_cast<Pool2D*>(l)) {
       if (!on || i < 2 || !(f[i - 2] & FF_FUSE_POOL)) pool->set_fused_producer(nullptr);
+      // average pool -> flatten -> dense closing the sequence: the classifier head
+      pool->set_head_dense(on && (f[i] & FF_FUSE_HEAD) ? static_cast<Dense*>(seq[i + 2].get()) : nullptr);
+    } else if (auto* flat = dynamic_cast<Flatten*>(l)) {
+      flat->set_head_dense(on && i >= 1 && (f[i - 1] & FF_FUSE_HEAD) ? static_cast<Dense*>(seq[i + 1].get()) : nullptr);
+    } else if (auto* dense = dynamic_cast<Dense*>(l)) {
+      dense->set_head_pool(on && i >= 2 && (f[i - 2] & FF_FUSE_HEAD) ? static_cast<Pool2D*>(seq[i - 2].get()) : nullptr);
     }
   }
 }
@@ -1212,8 +1276,14 @@ Tensor Pool2D::forward(const Tensor& x, bool training) {
   std::vector<int64_t>& in_shape_ = mbc().shape;
   check_act(x, dev_, "pool2d");
   const PoolShape p = shape_for(x.shape());
-  Tensor y = act_empty({p.N, p.C, p.OH, p.OW}, dev_);
   in_shape_ = x.shape();
+  if (head_ != nullptr && training && !max_) {
+    // the classifier head: this pool and the dense layer two layers on in one kernel
+    head_->set_micro_batch(mb_);
+    Tensor pooled;
+    if (head_->run_head(x, p, pooled)) return pooled;
+  }
+  Tensor y = act_empty({p.N, p.C, p.OH, p.OW}, dev_);
   if (max_) {
     const int64_t n = (int64_t)p.N * p.C * p.OH * p.OW;
     if (dev_.is_gpu()) {
@@ -1232,6 +1302,10 @@ Tensor Pool2D::forward(const Tensor& x, bool training) {
 }
 
 Tensor Pool2D::backward(const Tensor& dy) {
+  if (head_ != nullptr) {
+    head_->set_micro_batch(mb_);
+    if (head_->is_head_dx(dy, true)) return dy;  // (Dense::backward computed this gradient)
+  }
   const Tensor& idx_ = mbc().a;
   const std::vector<int64_t>& in_shape_ = mbc().shape;
   const PoolShape p = shape_for(in_shape_);
@@ -1279,6 +1353,10 @@ Tensor Flatten::forward(const Tensor& x, bool training) {
 }
 
 Tensor Flatten::backward(const Tensor& dy) {
+  if (head_ != nullptr) {
+    head_->set_micro_batch(mb_);
+    if (head_->is_head_dx(dy, false)) return dy;  // (the pool's input gradient, from Dense::backward)
+  }
   const std::vector<int64_t>& in_shape_ = mbc().shape;
   const int64_t HW = in_shape_[2] * in_shape_[3];
   if (!dev_.is_gpu()) return dy.view(in_shape_);

@@ -861,6 +861,21 @@ void dense_wgrad(const void* dy, const void* x, float* gw, float* gb, int N, int
   });
 }
 
+bool head_supported(const PoolShape& p, int Out) { return dcnn::head_supported(geom(p), Out); }
+
+void head_fwd(const void* x, const void* w, const float* bias, void* pooled, void* y, const PoolShape& p, int Out) {
+  dcnn::head_fwd(static_cast<const bf16*>(x), static_cast<const bf16*>(w), bias, static_cast<bf16*>(pooled),
+                 static_cast<bf16*>(y), geom(p), Out, cur());
+}
+
+void head_bwd(const void* dy, const void* w, const void* pooled, void* dx, float* gw, float* gb, const PoolShape& p,
+              int Out) {
+  wgrad_split(head_bwd_splits(p.N, p.C, Out), (long)Out * p.C, Out, gw, gb, [&](float* slab, float* bslab) {
+    dcnn::head_bwd(static_cast<const bf16*>(dy), static_cast<const bf16*>(w), static_cast<const bf16*>(pooled),
+                   static_cast<bf16*>(dx), slab, bslab, geom(p), Out, cur());
+  });
+}
+
 // deterministic slab statistics: (pointer, parts) for bn_apply / bn_bwd_apply
 static std::pair<const float*, int> reduce_stats(int mode, const float* slab, int rows, int C) {
   const int parts = bn_stat_parts(rows);

@@ -201,6 +201,8 @@ int get_f32_mode();
 void conv_weight_transpose_f32(const float* w, float* wt, int Co, int T_, int Ci, hipStream_t s);
 void gemm_tn(TnArgs a, int splits, hipStream_t s);
 int gemm_tn_splits(int M, int N, int P);
+int gemm_tn_k_per_split(int P, int splits);  // reduction rows per split
+int gemm_tn_bias_rows(int M);                // interleaved bias-gradient partials per output row
 // The shared conv routing table (conv_route.cpp): which kernel family runs a bf16 convolution,
 // asked by both front ends (ops/hip.py and the C++ host API's GPU backend). g1s_mode: the
 // streaming kernel's epilogue mode the caller needs (forward 0 / 1 = statistics, dgrad 0 / 2 =
@@ -275,6 +277,19 @@ void maxpool_bwd_bnb(const bf16* dy, const uint8_t* idx, const bf16* ypool, cons
                      const float* istd, bf16* dx, PoolGeom g, float* slab, float* zero_sums, hipStream_t s);
 void avgpool_fwd(int dt, const void* x, void* y, PoolGeom g, hipStream_t s);
 void avgpool_bwd(int dt, const void* dy, void* dx, PoolGeom g, hipStream_t s);
+// The classifier head fused (head.hip; bf16): g is the average pool's geometry (C = the FC's input
+// features), w the FC weights [Out][C] as stored, bias fp32 (optional). Supported: the pool window
+// is the whole map (one output pixel; the stride plays no part), no padding, C % 64 == 0,
+// C <= 2048, N >= 1, Out >= 1; the launchers throw std::invalid_argument on anything else.
+bool head_supported(PoolGeom g, int Out);
+// pooled[N][C] = bf16(mean over the map), logits[N][Out] = bf16(pooled . w^T + bias)
+void head_fwd(const bf16* x, const bf16* w, const float* bias, bf16* pooled, bf16* logits, PoolGeom g, int Out,
+              hipStream_t s);
+// dx[N][H][W][C] = bf16(bf16(dlogits . w) / (H W)) (dx null: not computed), and the FC gradients as
+// slab [splits][Out][C] (+ bias_slab [splits][Out], optional) for splitk_reduce*, splits as below
+int head_bwd_splits(int N, int In, int Out);
+void head_bwd(const bf16* dlogits, const bf16* w, const bf16* pooled, bf16* dx, float* slab, float* bias_slab,
+              PoolGeom g, int Out, hipStream_t s);
 void act_fwd(int dt, const void* x, void* y, long n, int type, float a, hipStream_t s);
 void act_bwd(int dt, const void* x, const void* dy, void* dx, long n, int type, float a, hipStream_t s);
 void softmax_rows(int dt, const void* x, void* y, long rows, int C, hipStream_t s);

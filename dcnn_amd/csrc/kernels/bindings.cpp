@@ -240,7 +240,9 @@ PYBIND11_MODULE(_kernels, m) {
                          {"FK_RELU", FK_RELU}, {"FK_ACT", FK_ACT}, {"FK_MAXPOOL", FK_MAXPOOL},
                          {"FF_EMIT_BN_STATS", FF_EMIT_BN_STATS}, {"FF_FUSE_RELU", FF_FUSE_RELU},
                          {"FF_PASSTHROUGH", FF_PASSTHROUGH}, {"FF_FUSE_POOL", FF_FUSE_POOL},
-                         {"FF_BNB_CONSUMER", FF_BNB_CONSUMER}, {"RF_FUSED_TAIL", RF_FUSED_TAIL},
+                         {"FF_BNB_CONSUMER", FF_BNB_CONSUMER}, {"FK_AVGPOOL", FK_AVGPOOL},
+                         {"FK_FLATTEN", FK_FLATTEN}, {"FK_DENSE", FK_DENSE}, {"FF_FUSE_HEAD", FF_FUSE_HEAD},
+                         {"RF_FUSED_TAIL", RF_FUSED_TAIL},
                          {"RF_DUAL_SHORTCUT", RF_DUAL_SHORTCUT}})
     m.attr(name) = v;
   m.def("g1s_rows", &g1s_rows);
@@ -458,6 +460,24 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("avgpool_bwd", [geom](int dt, uintptr_t dy, uintptr_t dx, int N, int H, int W, int C, int OH, int OW, int ph,
                               int pw, int sh, int sw, int padh, int padw, uintptr_t st) {
     avgpool_bwd(dt, P<const void*>(dy), P<void*>(dx), geom(N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw), S(st));
+  });
+  // the fused classifier head (head.hip): the average pool's geometry, then the FC's class count
+  m.def("head_supported", [geom](int N, int H, int W, int C, int OH, int OW, int ph, int pw, int sh, int sw, int padh,
+                                 int padw, int Out) {
+    return head_supported(geom(N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw), Out);
+  });
+  m.def("head_fwd", [geom](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t pooled, uintptr_t logits, int N, int H,
+                           int W, int C, int OH, int OW, int ph, int pw, int sh, int sw, int padh, int padw, int Out,
+                           uintptr_t st) {
+    head_fwd(P<const bf16*>(x), P<const bf16*>(w), P<const float*>(bias), P<bf16*>(pooled), P<bf16*>(logits),
+             geom(N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw), Out, S(st));
+  });
+  m.def("head_bwd_splits", &head_bwd_splits);
+  m.def("head_bwd", [geom](uintptr_t dlogits, uintptr_t w, uintptr_t pooled, uintptr_t dx, uintptr_t slab,
+                           uintptr_t bias_slab, int N, int H, int W, int C, int OH, int OW, int ph, int pw, int sh,
+                           int sw, int padh, int padw, int Out, uintptr_t st) {
+    head_bwd(P<const bf16*>(dlogits), P<const bf16*>(w), P<const bf16*>(pooled), P<bf16*>(dx), P<float*>(slab),
+             P<float*>(bias_slab), geom(N, H, W, C, OH, OW, ph, pw, sh, sw, padh, padw), Out, S(st));
   });
   m.def("act_fwd", [](int dt, uintptr_t x, uintptr_t y, long n, int type, float a, uintptr_t st) {
     act_fwd(dt, P<const void*>(x), P<void*>(y), n, type, a, S(st));

@@ -32,6 +32,8 @@ std::vector<int> plan_sequence_fusions(const std::vector<int>& kinds) {
     if (!is(j, FK_CONV)) continue;
     if (is(j - 1, FK_BN) || (j >= 2 && is(j - 1, FK_RELU) && is(j - 2, FK_BN))) f[j] |= FF_BNB_CONSUMER;
   }
+  // ... -> average pool -> flatten -> dense, closing the sequence: the classifier head
+  if (n >= 3 && is(n - 3, FK_AVGPOOL) && is(n - 2, FK_FLATTEN) && is(n - 1, FK_DENSE)) f[n - 3] |= FF_FUSE_HEAD;
   return f;
 }
 

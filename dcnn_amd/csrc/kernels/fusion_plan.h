@@ -7,13 +7,20 @@
 namespace dcnn {
 
 // layer kinds in order -> per-layer FF_* flags
-enum FuseKind : int { FK_OTHER = 0, FK_CONV = 1, FK_BN = 2, FK_RELU = 3, FK_ACT = 4, FK_MAXPOOL = 5 };
+enum FuseKind : int {
+  FK_OTHER = 0, FK_CONV = 1, FK_BN = 2, FK_RELU = 3, FK_ACT = 4, FK_MAXPOOL = 5, FK_AVGPOOL = 6, FK_FLATTEN = 7,
+  FK_DENSE = 8
+};
 enum FuseFlag : int {
   FF_EMIT_BN_STATS = 1,  // conv: its epilogue emits the statistics rows of the BatchNorm after it
   FF_FUSE_RELU = 2,      // BatchNorm: its apply pass applies the ReLU after it
   FF_PASSTHROUGH = 4,    // ReLU: already applied by the BatchNorm before it
   FF_FUSE_POOL = 8,      // BatchNorm: its training apply also runs the max-pool two layers on
   FF_BNB_CONSUMER = 16,  // conv: its data gradient carries the backward of the BatchNorm [+ ReLU] before it
+  // average pool: the sequence ends average pool -> flatten -> dense, the classifier head; the
+  // pool's forward also runs the dense layer and the dense layer's backward also the pool's
+  // (head.hip, where the geometry allows; flatten passes through)
+  FF_FUSE_HEAD = 32,
 };
 std::vector<int> plan_sequence_fusions(const std::vector<int>& kinds);
 // residual block (main path kinds, shortcut kinds, block activation relu / linear / none):

@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_kernel(TnArgs p) {
     const char* Bs = As + A_BYTES;
     if (do_bias) {
       // column sums of the staged dY tile (conv / dense bias gradient)
-      constexpr int RSTEP = 256 / BM > 0 ? 256 / BM : 1;
+      constexpr int RSTEP = 256 / BM > 0 ? 256 / BM : 1;  // (= gemm_tn_bias_rows)
       const int col = tid % BM, r0 = tid / BM;
       if (tid < BM * RSTEP) {
         const int ch = col >> 3, w = (col & 7) * 2;
@@ -737,6 +737,13 @@ int gemm_tn_splits(int M, int N, int P) {
   return (int)splits;
 }
 
+// reduction rows per split (whole 64-row K-steps), and the number of interleaved partial sums per
+// output row of the bias gradient (256 threads over the BM-row tile: K-step row r goes to partial
+// r % rows, the partials are added in order). head.hip's weight blocks follow both, so that the
+// fused classifier head leaves the bits gemm_tn leaves.
+int gemm_tn_k_per_split(int P, int splits) { return ((P + splits - 1) / splits + 63) / 64 * 64; }
+int gemm_tn_bias_rows(int M) { return 256 / (M >= 128 ? 128 : 64); }
+
 void gemm_tn(TnArgs a, int splits, hipStream_t s) {
   const bool conv = a.mode == kConvFwd;
   const int bm = a.M >= 128 ? 128 : 64;
@@ -744,8 +751,7 @@ void gemm_tn(TnArgs a, int splits, hipStream_t s) {
   if (conv) while (bn > 32 && a.cs % bn != 0) bn >>= 1;
   const bool v = a.M % 8 == 0 && (conv ? a.cs % bn == 0 : (a.N % 8 == 0 && a.ldx % 8 == 0));
   if (!v) bn = a.N >= 128 ? 128 : 64;
-  const int per = (a.P + splits - 1) / splits;
-  a.k_per_split = ((per + 63) / 64) * 64;
+  a.k_per_split = gemm_tn_k_per_split(a.P, splits);
 #define DCNN_TN(BM, BN, V) if (bm == BM && bn == BN && v == V) return launch_tn<BM, BN, 64, V>(a, splits, s)
   DCNN_TN(128, 128, true);
   DCNN_TN(128, 64, true);
