@@ -85,6 +85,41 @@ int dcnn_c_conv_dgrad(const void* dy, const void* w, int w_t, void* dx, const in
   });
 }
 
+// dcnn_c_conv_dgrad (pre-transposed operand) with a phase-compact residual [N][H / SH][W / SW][C]
+// (gpu_ops::DgradOpts::residual_compact); bnb as dcnn_c_conv_dgrad
+int dcnn_c_conv_dgrad_compact_residual(const void* dy, const void* w, void* dx, const int* shape,
+                                       const void* residual, int bnb, const void* y_bn, const void* x_bn,
+                                       const float* mean, const float* istd, const float** slab, int* rows) {
+  return guarded([&] {
+    const ConvShape s = shape_of(shape);
+    int dev = 0;
+    Tensor wt = Tensor::empty({(int64_t)s.C * s.KH * s.KW * s.Co}, DType::BF16, Device::gpu(dev));
+    gpu_ops::weight_transpose(w, wt.data(), s.Co, s.KH * s.KW, s.C);
+    gpu_ops::BnbOperands ops{y_bn, x_bn, mean, istd};
+    gpu_ops::DgradOpts opt;
+    opt.residual_compact = true;
+    int r = 0;
+    const float* st = gpu_ops::conv_dgrad(dy, wt.data(), dx, s, residual, true, bnb ? &ops : nullptr, &r, opt);
+    if (slab) *slab = st;
+    if (rows) *rows = r;
+    gpu::synchronize();  // (wt is released after the kernels that read it)
+  });
+}
+
+// the [N][OH][OW][C] data gradient of a strided 1x1 pad-0 conv (gpu_ops::conv_dgrad_compact)
+int dcnn_c_conv_dgrad_compact(const void* dy, const void* w, void* dxc, const int* shape) {
+  return guarded([&] {
+    const ConvShape s = shape_of(shape);
+    int dev = 0;
+    Tensor wt = Tensor::empty({(int64_t)s.C * s.KH * s.KW * s.Co}, DType::BF16, Device::gpu(dev));
+    gpu_ops::weight_transpose(w, wt.data(), s.Co, s.KH * s.KW, s.C);
+    gpu_ops::conv_dgrad_compact(dy, wt.data(), dxc, s, true);
+    gpu::synchronize();
+  });
+}
+
+int dcnn_c_conv_dgrad_takes_compact(const int* shape) { return gpu_ops::conv_dgrad_takes_compact(shape_of(shape)) ? 1 : 0; }
+
 // gw / gb (+=) the weight / bias gradient; deferred: inside a backward's batched split-K reduce
 int dcnn_c_conv_wgrad(const void* dy, const void* x, float* gw, float* gb, const int* shape, int deferred) {
   return guarded([&] {

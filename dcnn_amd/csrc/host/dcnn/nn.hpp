@@ -132,6 +132,8 @@ class ConvBase : public Layer {
     (void)dy; (void)residual; (void)dx;
     return false;
   }
+  int stride_h() const { return sh_; }
+  int stride_w() const { return sw_; }
 
  protected:
   ConvBase(int in_ch, int out_ch, int kh, int kw, int groups, int sh, int sw, int ph, int pw, bool bias,
@@ -170,6 +172,14 @@ class Conv2D : public ConvBase {
   // the block output), applied only by backward_residual (after the shortcut gradient is added)
   void set_block_bnb_producer(class BatchNorm* bn) { bnb_block_from_ = bn; }
   bool backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) override;
+  // GPU, a downsample block's pair (ResidualBlock::backward). The shortcut's side: this 1x1 pad-0
+  // strided conv's data gradient only reaches the pixels (SH i, SW j), and backward_compact returns
+  // just those, (N, Ci, H / SH, W / SW), with the weight gradient as backward runs it. The head
+  // conv's side: backward_residual takes that tensor as `residual` when takes_compact_residual
+  // (same strides; its data gradient on the stride-phase-grouped gemm_g2 launch)
+  bool compact_grad_ok() const;
+  Tensor backward_compact(const Tensor& dy);
+  bool takes_compact_residual(int sh, int sw) const;
   // GPU RGB stem (the network input, fp32, on the stem kernel): true when this micro-batch's
   // forward ran it, so backward_stem_bn applies
   bool ran_stem() const;

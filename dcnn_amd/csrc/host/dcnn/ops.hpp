@@ -99,8 +99,26 @@ struct BnbOperands {
 // bnb: the epilogue also masks dx with y > 0 and writes the producing BatchNorm's backward
 // statistics ([rows][2][C] sums of dx' and dx' * xhat) — returns that slab (valid until the next
 // conv_dgrad) and sets *bnb_rows; 0 / nullptr when the route has no such epilogue (dx is plain)
+// opt.residual_compact: `residual` is [N][H / SH][W / SW][C], the shortcut gradient at the pixels
+// (SH i, SW j) only (conv_dgrad_compact's result) — taken on the grouped gemm_g2 route alone
+// (conv_dgrad_takes_compact), any other route throws; opt.dense_g2: a 1x1 stride-1 data gradient
+// on the dense gemm_g2 kernel whatever the routing table says (throws when gemm_g2 cannot run it)
+struct DgradOpts {
+  bool residual_compact = false;
+  bool dense_g2 = false;
+};
 const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, const void* residual = nullptr,
-                        bool w_transposed = false, const BnbOperands* bnb = nullptr, int* bnb_rows = nullptr);
+                        bool w_transposed = false, const BnbOperands* bnb = nullptr, int* bnb_rows = nullptr,
+                        DgradOpts opt = {});
+// the data gradient of s takes a phase-compact residual: the stride-phase-grouped gemm_g2 route,
+// H and W multiples of the stride, a tap on phase (0, 0)
+bool conv_dgrad_takes_compact(const ConvShape& s);
+// a 1x1 pad-0 conv of stride > 1 (H, W multiples of it): its data gradient at the pixels
+// (SH i, SW j), the only ones it reaches, as [N][OH][OW][C] — the same weights' stride-1 data
+// gradient on dy's grid, on the kernel and in the K order of the full-size launch (same bits)
+void conv_dgrad_compact(const void* dy, const void* w, void* dxc, const ConvShape& s, bool w_transposed);
+// (DCNN_COMPACT_SHORTCUT_GRAD=0: a downsample block's shortcut gradient stays full-size — A/B hook)
+bool compact_shortcut_grad_enabled();
 // [Co][T][C] bf16 -> [C][T][Co]; the batched form takes a device table of rows
 // (src, dst, Co, T, C) and the largest 64x64-tile count per tap over the rows
 void weight_transpose(const void* w, void* wt, int Co, int T, int C);

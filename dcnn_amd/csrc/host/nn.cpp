@@ -283,11 +283,43 @@ Tensor Conv2D::backward(const Tensor& dy) {
   return dx;
 }
 
+bool Conv2D::compact_grad_ok() const {
+  const Tensor& x_ = const_cast<Conv2D*>(this)->mbc().a;
+  if (!dev_.is_gpu() || !x_.defined() || x_.dtype() != DType::BF16 || !input_grad_ || bnb_from_ != nullptr) return false;
+  const ConvShape s = shape_for(x_.shape());
+  return kh_ == 1 && kw_ == 1 && ph_ == 0 && pw_ == 0 && (sh_ > 1 || sw_ > 1) && s.H % sh_ == 0 && s.W % sw_ == 0 &&
+         ci_ % 8 == 0 && co_ % 8 == 0;
+}
+
+Tensor Conv2D::backward_compact(const Tensor& dy) {
+  if (!compact_grad_ok()) throw std::runtime_error(name_ + ": backward_compact is a strided 1x1 GPU conv's");
+  const Tensor& x_ = mbc().a;
+  const ConvShape s = shape_for(x_.shape());
+  gpu_ops::conv_wgrad(dy.data(), x_.data(), params_[0].grad.ptr<float>(), bias_grad(), s);
+  Tensor dxc = act_empty({s.N, s.C, s.OH, s.OW}, dev_);
+  bool tr = false;
+  const void* w = dgrad_operand(tr);
+  gpu_ops::conv_dgrad_compact(dy.data(), w, dxc.data(), s, tr);
+  return dxc;
+}
+
+bool Conv2D::takes_compact_residual(int sh, int sw) const {
+  const Tensor& x_ = const_cast<Conv2D*>(this)->mbc().a;
+  if (!dev_.is_gpu() || !x_.defined() || x_.dtype() != DType::BF16 || sh != sh_ || sw != sw_) return false;
+  return gpu_ops::conv_dgrad_takes_compact(shape_for(x_.shape()));
+}
+
 bool Conv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
   const Tensor& x_ = mbc().a;
-  if (!dev_.is_gpu() || x_.dtype() == DType::F32 || residual.shape() != x_.shape())
+  if (!dev_.is_gpu() || x_.dtype() == DType::F32)
     throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
   const ConvShape s = shape_for(x_.shape());
+  // a phase-compact residual (backward_compact of the block's strided 1x1 shortcut): its shape
+  gpu_ops::DgradOpts opt;
+  opt.residual_compact = residual.shape() != x_.shape() && (sh_ > 1 || sw_ > 1) && s.H % sh_ == 0 && s.W % sw_ == 0 &&
+                         residual.shape() == std::vector<int64_t>{s.N, s.C, s.H / sh_, s.W / sw_};
+  if (residual.shape() != x_.shape() && !opt.residual_compact)
+    throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
   float* gb = bias_grad();
   gpu_ops::conv_wgrad(dy.data(), x_.data(), params_[0].grad.ptr<float>(), gb, s);
   dx = act_empty(x_.shape(), dev_);
@@ -296,11 +328,11 @@ bool Conv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor&
   if (bnb_block_from_ != nullptr) {
     const gpu_ops::BnbOperands ops = bnb_block_from_->bnb_operands(mb_);
     int rows = 0;
-    const float* st = gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr, &ops, &rows);
+    const float* st = gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr, &ops, &rows, opt);
     if (rows > 0) bnb_block_from_->offer_bwd_stats(dx.data(), st, rows);
     return true;
   }
-  gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr);
+  gpu_ops::conv_dgrad(dy.data(), w, dx.data(), s, residual.data(), tr, nullptr, nullptr, opt);
   return true;
 }
 
@@ -1156,12 +1188,24 @@ Tensor ResidualBlock::backward(const Tensor& dy) {
   if (BatchNorm* tail = fused_tail()) {
     Tensor gs, gm;  // gs: the activation-masked dy, for the shortcut
     BatchNorm* sbn = dual_shortcut();
+    // a downsample block (strided 1x1 pad-0 shortcut conv, same-stride head conv on the grouped
+    // gemm_g2 data gradient): the shortcut's data gradient stays the (N, Ci, H / SH, W / SW)
+    // tensor of the pixels it reaches, and the head conv's phase (0, 0) class alone adds it —
+    // instead of a full-size tensor written three quarters zero and read back by every phase
+    auto* sconv = short_.empty() ? nullptr : dynamic_cast<Conv2D*>(short_[0].get());
+    auto* hconv = dynamic_cast<Conv2D*>(main_[0].get());
+    const bool compact = gpu_ops::compact_shortcut_grad_enabled() && dev_.is_gpu() && input_grad_ && sconv != nullptr &&
+                         hconv != nullptr && main_.size() > 1 && sconv->compact_grad_ok() &&
+                         hconv->takes_compact_residual(sconv->stride_h(), sconv->stride_w());
+    auto short_bwd = [&](size_t i, const Tensor& g) {
+      return i == 0 && compact ? sconv->backward_compact(g) : short_[i]->backward(g);
+    };
     if (sbn != nullptr && tail->backward_dual(dy, *sbn, gm, gs)) {
       // both BatchNorms' data gradients from one pass; gs is already below the shortcut BatchNorm
-      for (size_t i = short_.size() - 1; i-- > 0;) gs = short_[i]->backward(gs);
+      for (size_t i = short_.size() - 1; i-- > 0;) gs = short_bwd(i, gs);
     } else {
       gm = tail->backward_residual(dy, &gs);
-      for (size_t i = short_.size(); i-- > 0;) gs = short_[i]->backward(gs);
+      for (size_t i = short_.size(); i-- > 0;) gs = short_bwd(i, gs);
     }
     for (size_t i = main_.size() - 1; i-- > 1;) gm = main_[i]->backward(gm);
     // the main path's first conv adds the shortcut gradient in its data-gradient epilogue

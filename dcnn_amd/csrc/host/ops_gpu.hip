@@ -606,9 +606,63 @@ void multi_weight_transpose(const int64_t* table, int n, long max_tiles) {
   dcnn::multi_weight_transpose(table, n, max_tiles, cur());
 }
 
+namespace {
+// the stride-phase-grouped gemm_g2 data gradient runs p: equal phase grids, at most 4 of them,
+// and (more than one phase) class rows a multiple of the largest row tile
+bool g2_phases_ok(const ConvShape& s, const DgradPhases& p) {
+  const std::vector<DgradPhase>& cls = p.phases;
+  if (cls.empty() || cls.size() > 4 || p.taps.size() > 64) return false;
+  for (const DgradPhase& c : cls)
+    if (c.GH != cls[0].GH || c.GW != cls[0].GW) return false;
+  const long rows = (long)s.N * cls[0].GH * cls[0].GW;
+  return cls.size() == 1 || rows % 128 == 0;
+}
+bool g2_bytes_ok(const ConvShape& s) {
+  const long dyb = (long)s.N * s.OH * s.OW * s.Co * 2, wtb = (long)s.C * s.KH * s.KW * s.Co * 2;
+  return dyb < (1l << 31) && wtb < (1l << 31);
+}
+}  // namespace
+
+bool compact_shortcut_grad_enabled() {
+  static const bool on = [] {
+    const char* v = std::getenv("DCNN_COMPACT_SHORTCUT_GRAD");
+    return !(v && std::string(v) == "0");
+  }();
+  return on;
+}
+
+bool conv_dgrad_takes_compact(const ConvShape& s) {
+  if ((s.SH < 2 && s.SW < 2) || s.H % s.SH || s.W % s.SW || s.C % 8 || s.Co % 8) return false;
+  // (the residual needs none of the fused BatchNorm backward's operands: both g1s modes route alike)
+  const ConvRouteGeom g = route_geom(s, 0);
+  const int route = conv_dgrad_route(g);
+  if (route == ROUTE_HALO || route == ROUTE_G1S || route == ROUTE_GENERIC || !g2_bytes_ok(s)) return false;
+  const DgradPhases p = conv_dgrad_phases(g);
+  if (p.phases.size() < 2 || !g2_phases_ok(s, p)) return false;
+  for (const DgradPhase& c : p.phases)
+    if (c.ry == 0 && c.rx == 0) return c.nt > 0 && c.GH == s.H / s.SH && c.GW == s.W / s.SW;
+  return false;
+}
+
+void conv_dgrad_compact(const void* dy, const void* w, void* dxc, const ConvShape& s, bool w_transposed) {
+  if (s.KH != 1 || s.KW != 1 || s.PH != 0 || s.PW != 0 || (s.SH < 2 && s.SW < 2) || s.H % s.SH || s.W % s.SW ||
+      s.OH != s.H / s.SH || s.OW != s.W / s.SW)
+    throw std::invalid_argument("conv_dgrad_compact: a 1x1 pad-0 conv of stride > 1 on a map its stride divides");
+  // one tap, one phase: [Co][1][C] <-> [C][1][Co] weights as they are, dy's grid as the input grid
+  const ConvShape c{s.N, s.C, s.OH, s.OW, s.Co, 1, 1, 1, 1, 0, 0, s.OH, s.OW};
+  DgradOpts opt;
+  opt.dense_g2 = true;
+  conv_dgrad(dy, w, dxc, c, nullptr, w_transposed, nullptr, nullptr, opt);
+}
+
 const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, const void* residual,
-                        bool w_transposed, const BnbOperands* bnb, int* bnb_rows) {
+                        bool w_transposed, const BnbOperands* bnb, int* bnb_rows, DgradOpts opt) {
   const int T = s.KH * s.KW, K = T * s.Co;
+  if (opt.residual_compact && (residual == nullptr || !conv_dgrad_takes_compact(s)))
+    throw std::invalid_argument("conv_dgrad: a phase-compact residual is taken by the grouped gemm_g2 route only");
+  if (opt.dense_g2 && (T != 1 || s.SH != 1 || s.SW != 1 || s.PH != 0 || s.PW != 0 || bnb != nullptr ||
+                       s.C % 8 || s.Co % 8 || !g2_bytes_ok(s)))
+    throw std::invalid_argument("conv_dgrad: dense_g2 is a plain 1x1 stride-1 data gradient on gemm_g2");
   if (bnb_rows) *bnb_rows = 0;
   BnbArgs ba{};
   if (bnb) {
@@ -640,9 +694,10 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
   const long dyb = (long)s.N * s.OH * s.OW * s.Co * 2, wtb = (long)s.C * T * s.Co * 2;
   // shared routing table (conv_route.cpp); g1s mode 2: the streaming dgrad with the BN epilogue
   const ConvRouteGeom g = route_geom(s, bnb ? 2 : 0);
-  const int route = conv_dgrad_route(g);
+  const int route = opt.dense_g2 ? (int)ROUTE_GEMM_G2 : conv_dgrad_route(g);
   rec("dgrad", s, route, {{"residual", residual != nullptr}, {"w_t", w_transposed}, {"bnb", bnb != nullptr},
-                         {"bnb_mask", bnb != nullptr && bnb->y != nullptr}});
+                         {"bnb_mask", bnb != nullptr && bnb->y != nullptr},
+                         {"residual_compact", opt.residual_compact}});
   if (route == ROUTE_HALO && dyb < (1l << 31)) {
     // transposed conv of a stride-1 'same' conv: tap (ky, kx) reads dy at (PH - ky, PW - kx)
     HConvArgs a = hconv_dgrad_args(dy, wt, dx, residual, g);
@@ -667,11 +722,8 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
     const DgradPhases p = conv_dgrad_phases(g);
     const std::vector<DgradPhase>& cls = p.phases;
     if (p.taps.size() > 64) throw std::runtime_error("conv_dgrad: more than 64 taps");
-    bool uniform = true;
-    for (const DgradPhase& c : cls) uniform = uniform && c.GH == cls[0].GH && c.GW == cls[0].GW;
-    const long rows = (long)s.N * (cls.empty() ? 0 : cls[0].GH * cls[0].GW);
-    if (uniform && !cls.empty() && cls.size() <= 4 && (cls.size() == 1 || rows % 128 == 0)) {
-      G2Args a = g2_dgrad_args(dy, wt, dx, residual, g, p);
+    if (g2_phases_ok(s, p)) {
+      G2Args a = g2_dgrad_args(dy, wt, dx, residual, g, p, opt.residual_compact);
       // the producing BatchNorm's mask + backward statistics in the epilogue when every stride
       // phase has taps (a zero-tap phase's rows are written by the fill path, not the MMA epilogue)
       bool all_taps = true;
@@ -684,6 +736,7 @@ const float* conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape
       return a.stats;
     }
   }
+  if (opt.residual_compact || opt.dense_g2) throw std::runtime_error("conv_dgrad: gemm_g2 did not take the shape");
   NtArgs a{static_cast<const bf16*>(dy), wt, dx, s.N * s.H * s.W, s.C, K, 0, K, s.C, kConvDgrad, s.N, s.OH, s.OW,
            s.Co, s.H, s.W, s.KH, s.KW, s.SH, s.SW, s.PH, s.PW, nullptr, static_cast<const bf16*>(residual), nullptr,
            0, 0};

@@ -50,6 +50,11 @@ struct G2Args {
   // multiply-shift reciprocals of GH * GW and GW (set by gemm_g2(): the per-row pixel decode of
   // the A loader and the epilogue without run-time integer divisions; common.h FastDiv layout)
   unsigned fd_ghw[3], fd_gw[3];
+  // phase-compact residual of a grouped launch: res_cls >= 0 names the one row class whose rows
+  // have a residual, and `residual` is then a compact [NB][GH][GW][ldc] tensor indexed by that
+  // class's own rows (the other classes add +0.0 without a load: what a full-size residual that
+  // is zero off that phase gives, bit for bit). < 0 (the default): every class, full-size.
+  int res_cls = -1;
 };
 struct T2Args {
   const bf16* dY; const bf16* X; float* slab; float* bias_slab;

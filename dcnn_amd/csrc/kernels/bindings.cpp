@@ -34,7 +34,7 @@ static void bind_gemm_g2(int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigne
                          int Cs, int H, int W, int GH, int GW, int SY, int SX, const ConvTaps& taps, int ldb, int ldc,
                          int OH, int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual,
                          uintptr_t stats, int relu, uintptr_t zero_ptr, int zero_n, Ptr4 bnb, uintptr_t stream,
-                         const std::vector<std::array<int, 4>>& classes) {
+                         const std::vector<std::array<int, 4>>& classes, int res_cls) {
   const char* who = f32 ? "gemm_g2f" : "gemm_g2";
   if (f32 && bnb[1]) throw std::runtime_error("gemm_g2f: backward-BN epilogue fusion is bf16-only");
   G2Args a{};
@@ -47,6 +47,7 @@ static void bind_gemm_g2(int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigne
   a.bias = P<const float*>(bias); a.residual = P<const bf16*>(residual); a.stats = P<float*>(stats); a.relu = relu;
   a.zero_ptr = P<float*>(zero_ptr); a.zero_n = zero_n;
   a.bnb = bnb_of(bnb);
+  a.res_cls = res_cls;
   if (f32)
     gemm_g2f(a, S(stream));
   else
@@ -195,13 +196,22 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("conv_weight_transpose_f32", [](uintptr_t w, uintptr_t wt, int Co, int T_, int Ci, uintptr_t st) {
     conv_weight_transpose_f32(P<const float*>(w), P<float*>(wt), Co, T_, Ci, S(st));
   });
-  m.def("gemm_g2", &bind_gemm_g2);
+  m.def("gemm_g2", [](int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M, int N,
+                      int Cs, int H, int W, int GH, int GW, int SY, int SX, const ConvTaps& taps, int ldb, int ldc, int OH,
+                      int OW, int OSY, int OSX, int ORY, int ORX, uintptr_t bias, uintptr_t residual, uintptr_t stats,
+                      int relu, uintptr_t zero_ptr, int zero_n, Ptr4 bnb, uintptr_t stream,
+                      const std::vector<std::array<int, 4>>& classes) {
+    bind_gemm_g2(f32, A, B, C, a_bytes, b_bytes, M, N, Cs, H, W, GH, GW, SY, SX, taps, ldb, ldc, OH, OW, OSY, OSX, ORY, ORX,
+                 bias, residual, stats, relu, zero_ptr, zero_n, bnb, stream, classes, -1);
+  });
+  // gemm_g2 with a phase-compact residual (G2Args::res_cls: the last argument)
+  m.def("gemm_g2_res_cls", &bind_gemm_g2);
   // C[M][N] = A[M][K] . B[N][K]^T with the gathered GEMM's epilogue: one tap, a 1 x 1 grid per row
   m.def("gemm_g2_plain", [](int f32, uintptr_t A, uintptr_t B, uintptr_t C, unsigned a_bytes, unsigned b_bytes, int M,
                             int N, int K, uintptr_t bias, uintptr_t residual, uintptr_t stats, int relu,
                             uintptr_t zero_ptr, int zero_n, uintptr_t stream) {
     bind_gemm_g2(f32, A, B, C, a_bytes, b_bytes, M, N, K, 1, 1, 1, 1, 1, 1, {{0, 0, 0, 0}}, K, N, 1, 1, 1, 1, 0, 0, bias,
-                 residual, stats, relu, zero_ptr, zero_n, Ptr4{0, 0, 0, 0}, stream, {});
+                 residual, stats, relu, zero_ptr, zero_n, Ptr4{0, 0, 0, 0}, stream, {}, -1);
   });
   m.def("gemm_g2_stat_rows", &gemm_g2_stat_rows);
   for (auto [name, fn] : {std::pair<const char*, int (*)(ConvRouteGeom)>{"conv_fwd_route", &conv_fwd_route},

@@ -86,7 +86,7 @@ HConvArgs hconv_dgrad_args(const void* dy, const void* wt, void* dx, const void*
 }
 
 G2Args g2_dgrad_args(const void* dy, const void* wt, void* dx, const void* residual, const ConvRouteGeom& g,
-                     const DgradPhases& p) {
+                     const DgradPhases& p, bool residual_compact) {
   const DgradPhase& c0 = p.phases.at(0);
   G2Args a{};
   a.A = static_cast<const bf16*>(dy); a.B = static_cast<const bf16*>(wt); a.C = static_cast<bf16*>(dx);
@@ -101,6 +101,15 @@ G2Args g2_dgrad_args(const void* dy, const void* wt, void* dx, const void* resid
     std::vector<std::array<int, 4>> cls;
     for (const DgradPhase& c : p.phases) cls.push_back({c.t0, c.nt, c.ry, c.rx});
     set_classes(a, cls, "conv_dgrad");
+  }
+  if (residual_compact) {
+    // the residual covers the pixels (SH i, SW j) only: the phase (ry, rx) = (0, 0), as its class
+    if (residual == nullptr || p.phases.size() < 2)
+      throw std::runtime_error("conv_dgrad: a phase-compact residual needs a strided grouped launch and a residual");
+    for (size_t k = 0; k < p.phases.size(); ++k)
+      if (p.phases[k].ry == 0 && p.phases[k].rx == 0) a.res_cls = (int)k;
+    if (a.res_cls < 0 || p.phases[a.res_cls].nt < 1)
+      throw std::runtime_error("conv_dgrad: no tap reaches the phase (0, 0) of a phase-compact residual");
   }
   return a;
 }

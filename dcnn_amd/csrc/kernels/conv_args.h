@@ -72,9 +72,11 @@ G2Args g2_fwd_args(const void* x, const void* w, void* y, const float* bias, con
 HConvArgs hconv_fwd_args(const void* x, const void* w, void* y, const float* bias, const ConvRouteGeom& g);
 // halo data gradient of a stride-1 'same' conv: a 'same' conv of dy with the flipped taps
 HConvArgs hconv_dgrad_args(const void* dy, const void* wt, void* dx, const void* residual, const ConvRouteGeom& g);
-// every phase of p (equal GH x GW) as the row classes of one grouped launch; one phase: ungrouped
+// every phase of p (equal GH x GW) as the row classes of one grouped launch; one phase: ungrouped.
+// residual_compact: `residual` is [N][GH][GW][C], the gradient at the pixels (SH i, SW j) only (a
+// strided 1x1 pad-0 shortcut's) and zero elsewhere: G2Args::res_cls = the class of phase (0, 0)
 G2Args g2_dgrad_args(const void* dy, const void* wt, void* dx, const void* residual, const ConvRouteGeom& g,
-                     const DgradPhases& p);
+                     const DgradPhases& p, bool residual_compact = false);
 T2Args t2_wgrad_args(const void* dy, const void* x, float* slab, float* bias_slab, const ConvRouteGeom& g);
 // hwgrad (stride 1 'same': the input grid) or, s2, hwgrad_s2 (3x3 stride 2: dY's grid, no tap table)
 HWArgs hwgrad_args(const void* dy, const void* x, float* slab, float* bias_slab, const ConvRouteGeom& g, bool s2);

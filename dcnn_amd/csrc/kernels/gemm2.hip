@@ -72,8 +72,8 @@ struct G2 {
 // LDS ([BM][EPI_PITCH]) -> 16-byte rows to global (+residual, ReLU, backward-BN mask) and the
 // BatchNorm statistics rows of the stored values. All 256 threads; holds barriers.
 template <int BM, int BN, int EPI_PITCH>
-__device__ __forceinline__ void g2_epilogue2(const G2Args& p, char* smem, int m0, int n0, int tm, int mcls, int ory,
-                                             int orx) {
+__device__ __forceinline__ void g2_epilogue2(const G2Args& p, char* smem, int m0, int n0, int tm, int cls, int mcls,
+                                             int ory, int orx) {
   const int tid = threadIdx.x;
   // ---- epilogue 2: 16-byte rows -> global (+residual, ReLU, BN partial stats) ----
   constexpr int CG = BN / 8;           // column groups of 8
@@ -105,6 +105,11 @@ __device__ __forceinline__ void g2_epilogue2(const G2Args& p, char* smem, int m0
   // every row's operands are loaded before the first store: a load's wait also waits for every
   // older store, and one latency per tile instead of one per row matters at 2 waves per SIMD
   const bool has_res = p.residual != nullptr, has_y = bnb && p.bnb.y != nullptr, has_x = bnb && p.stats;
+  // phase-compact residual (G2Args::res_cls): only that class's tiles load it, at the class's own
+  // row; the others keep the zero chunk, so their `f + 0.0f` below is what a full-size residual
+  // that is zero off the phase gave (-0.0 accumulators still become +0.0)
+  const bool res_compact = p.res_cls >= 0;
+  const bool load_res = has_res && (!res_compact || cls == p.res_cls);
   constexpr int NR = BM / RSTEP;       // rows per thread
   uint4 c_res[NR], c_y[NR], c_x[NR];
 #pragma unroll
@@ -113,7 +118,8 @@ __device__ __forceinline__ void g2_epilogue2(const G2Args& p, char* smem, int m0
     const int row = r0 + i * RSTEP;
     if (m0 + row >= p.M || !col_ok) continue;
     const long o = orow_of(row) * p.ldc + ncol;
-    if (has_res) c_res[i] = *reinterpret_cast<const uint4*>(p.residual + o);
+    if (load_res)
+      c_res[i] = *reinterpret_cast<const uint4*>(p.residual + (res_compact ? (long)(m0 + row - mcls) * p.ldc + ncol : o));
     if (has_y) c_y[i] = *reinterpret_cast<const uint4*>(p.bnb.y + o);
     if (has_x) c_x[i] = *reinterpret_cast<const uint4*>(p.bnb.x + o);
   }
@@ -425,7 +431,7 @@ __global__ void __launch_bounds__(256, 2) gemm_g2_kernel(G2Args p) {
       }
   }
   __syncthreads();
-  g2_epilogue2<BM, BN, T::EPI_PITCH>(p, smem, m0, n0, tm, mcls, ory, orx);
+  g2_epilogue2<BM, BN, T::EPI_PITCH>(p, smem, m0, n0, tm, cls, mcls, ory, orx);
 }
 
 constexpr int kG2MaxSplit = 8;  // K slices of the split-K path at most
@@ -487,7 +493,7 @@ __global__ void __launch_bounds__(256, 2) g2_splitk_epi_kernel(G2Args p) {
     }
   }
   __syncthreads();
-  g2_epilogue2<BM, BN, EPI_PITCH>(p, smem, m0, n0, tm, 0, p.cls_ory[0], p.cls_orx[0]);
+  g2_epilogue2<BM, BN, EPI_PITCH>(p, smem, m0, n0, tm, 0, 0, p.cls_ory[0], p.cls_orx[0]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -866,6 +872,14 @@ void gemm_g2(const G2Args& a_in, hipStream_t s) {
     for (int c = 0; c < a.ncls; ++c)
       if (a.cls_nt[c] < 0 || a.cls_t0[c] < 0 || a.cls_t0[c] + a.cls_nt[c] > a.ntaps)
         throw std::runtime_error("gemm_g2: class tap range out of bounds");
+  }
+  if (a.res_cls >= 0) {  // phase-compact residual: a grouped launch, a class in range that has taps
+    if (a.ncls <= 1 || a.residual == nullptr)
+      throw std::runtime_error("gemm_g2: a phase-compact residual needs a grouped launch with a residual");
+    if (a.res_cls >= a.ncls) throw std::runtime_error("gemm_g2: res_cls out of range");
+    if (a.cls_nt[a.res_cls] < 1) throw std::runtime_error("gemm_g2: res_cls names a class without taps");
+  } else {
+    a.res_cls = -1;
   }
   {
     const FastDiv f1 = make_fastdiv((unsigned)(a.GH * a.GW)), f2 = make_fastdiv((unsigned)a.GW);

@@ -901,6 +901,7 @@ static int g2f_bm(int M, int N) { return g2f_bn(M, N) ? 128 : FBM; }
 
 void gemm_g2f(const G2Args& a, hipStream_t s) {
   if (a.ntaps > 64) throw std::runtime_error("gemm_g2f: at most 64 taps");
+  if (a.res_cls >= 0) throw std::runtime_error("gemm_g2f: the phase-compact residual is bf16-only");
   const int bn = f32_split() ? 0 : g2f_bn(a.M, a.N);
   if (f32_split()) {
     const int tiles = ((a.M + FBM - 1) / FBM) * ((a.N + FBN - 1) / FBN);

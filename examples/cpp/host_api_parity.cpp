@@ -13,6 +13,9 @@
 //                                              and the batch (prefix.x.bin, prefix.y.bin)
 //   host_api_parity blocks <model_name> <batch> [--device GPU]
 //                                              teacher-forced per-layer errors against the CPU backend
+//   host_api_parity resblock <in> <out> <hw> <batch> <out.bin> [--device GPU]
+//                                              one stride-2 basic residual block, forward + backward on
+//                                              fixed data; its input gradient and parameter gradients
 //   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph]
 //                                              Adam steps on a synthetic set, then save
 // Output is plain text: one "key v0 v1 ..." line per item.
@@ -133,6 +136,44 @@ int main(int argc, char** argv) {
       m.backward(r.grad);
       std::ofstream f(argv[4], std::ios::binary);
       std::printf("loss %.9g\nparams", r.loss);
+      for (Param* p : m.parameters()) {
+        p->grad.view(p->shape, p->layout).save(f);
+        std::printf(" %s", p->name.c_str());
+      }
+      std::printf("\n");
+      return 0;
+    }
+    if (cmd == "resblock" && argc >= 7) {
+      // one basic downsample residual block (stride 2, projection shortcut) alone: forward and
+      // backward on fixed pseudo-random data; the input gradient, then every parameter gradient
+      const Device dev = device_arg(argc, argv);
+      const int in = std::atoi(argv[2]), out = std::atoi(argv[3]), hw = std::atoi(argv[4]), batch = std::atoi(argv[5]);
+      Sequential m = SequentialBuilder("downsample_block").input({in, hw, hw}).basic_residual_block(in, out, 2, "block").build();
+      m.set_device(dev);
+      m.initialize(11);
+      m.set_training(true);
+      uint32_t lcg = 12345u;
+      auto fill = [&](size_t n) {
+        std::vector<float> v(n);
+        for (float& f : v) {
+          lcg = lcg * 1664525u + 1013904223u;
+          f = ((float)(lcg >> 8) / (float)(1u << 24) - 0.5f) * 2.f;
+        }
+        return v;
+      };
+      auto act = [&](const std::vector<float>& v, const std::vector<int64_t>& shape) {
+        return Tensor::from_host(v, shape, dev, dev.is_gpu() ? DType::BF16 : DType::F32,
+                                 dev.is_gpu() ? Layout::NHWC : Layout::NCHW);
+      };
+      Layer* block = m.layers()[0].get();
+      block->set_input_grad(true);
+      m.zero_grad();
+      const Tensor x = act(fill((size_t)batch * in * hw * hw), {batch, in, hw, hw});
+      const Tensor y = block->forward(x, true);
+      const Tensor dx = block->backward(act(fill((size_t)y.numel()), y.shape()));
+      std::ofstream f(argv[6], std::ios::binary);
+      Tensor::from_host(dx.to_host_f32(), dx.shape(), Device::cpu()).save(f);
+      std::printf("params dx");
       for (Param* p : m.parameters()) {
         p->grad.view(p->shape, p->layout).save(f);
         std::printf(" %s", p->name.c_str());
