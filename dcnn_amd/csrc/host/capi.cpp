@@ -206,4 +206,27 @@ int dcnn_c_stem_wgrad(const void* dy, const float* x, float* gw, float* gb, cons
   });
 }
 
+// channel LayerNorm over bf16 NHWC rows [R][C]: y = (x - mean) rstd gamma + beta (gamma / beta null:
+// no affine), mean / rstd fp32 [R] saved
+int dcnn_c_layernorm_fwd(const void* x, void* y, long R, int C, const float* gamma, const float* beta, float eps,
+                         float* mean, float* rstd) {
+  return guarded([&] { gpu_ops::layernorm_fwd(x, y, R, C, gamma, beta, eps, mean, rstd); });
+}
+
+// dx of dcnn_c_layernorm_fwd; dgamma / dbeta (+=, may be null)
+int dcnn_c_layernorm_bwd(const void* dy, const void* x, void* dx, long R, int C, const float* gamma, const float* mean,
+                         const float* rstd, float* dgamma, float* dbeta) {
+  return guarded([&] { gpu_ops::layernorm_bwd(dy, x, dx, R, C, gamma, mean, rstd, dgamma, dbeta); });
+}
+
+// LayerScale: y = gamma[c] x (+ residual)
+int dcnn_c_layer_scale_fwd(const void* x, const float* gamma, const void* residual, void* y, long R, int C) {
+  return guarded([&] { gpu_ops::layer_scale_fwd(x, gamma, residual, y, R, C); });
+}
+
+// dx = gamma[c] dy, dgamma (+=) the sum of dy x
+int dcnn_c_layer_scale_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* dgamma, long R, int C) {
+  return guarded([&] { gpu_ops::layer_scale_bwd(dy, x, gamma, dx, dgamma, R, C); });
+}
+
 }  // extern "C"

@@ -209,6 +209,8 @@ class DepthwiseConv2D : public ConvBase {
                   std::string name = "depthwise_conv2d");
   std::string type() const override { return "depthwise_conv2d"; }
   json::Value parameters_config() const override;
+  // dx = conv^T(dy) + residual (GPU): wgrad + the fused data gradient
+  bool backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) override;
 
  protected:
   bool depthwise() const override { return true; }
@@ -368,6 +370,44 @@ class GroupNorm : public Layer {
   Tensor ident_, scratch_;
 };
 
+// Channel LayerNorm: every (n, h, w) position over its C channels (F.layer_norm over the channel
+// dimension; not GroupNorm(1, C), which normalises over C H W); gamma / beta per channel. GPU:
+// lnorm.hip. No reference counterpart.
+class LayerNorm : public Layer {
+ public:
+  explicit LayerNorm(int num_channels, float eps = 1e-6f, bool affine = true, std::string name = "layernorm");
+  std::string type() const override { return "layernorm"; }
+  json::Value parameters_config() const override;
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override { return in; }
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override;
+  Tensor backward(const Tensor& dy) override;
+
+ private:
+  int c_;
+  float eps_;
+  bool affine_;
+};
+
+// Learnable per-channel scale y = gamma[c] x (a ConvNeXt block's layer scale). Closing the main
+// path of an identity-shortcut block without activation it also adds the block input in its store
+// (forward_residual: ResidualBlock::scale_tail).
+class LayerScale : public Layer {
+ public:
+  explicit LayerScale(int num_channels, float init_value = 1e-6f, std::string name = "layer_scale");
+  std::string type() const override { return "layer_scale"; }
+  json::Value parameters_config() const override;
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override { return in; }
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override { return forward_residual(x, nullptr, training); }
+  Tensor forward_residual(const Tensor& x, const Tensor* residual, bool training);  // gamma x + residual
+  Tensor backward(const Tensor& dy) override;
+
+ private:
+  int c_;
+  float init_;
+};
+
 // inverted dropout (scale 1 / (1 - p)), identity in eval; the mask is a counter-based function
 // of (seed, element), regenerated in backward (reference include/nn/layers_impl/dropout_layer.tpp)
 class Dropout : public Layer {
@@ -455,6 +495,9 @@ class ResidualBlock : public Layer {
   // GPU: the projection shortcut's closing BatchNorm, paired with the fused tail
   // (BatchNorm::forward_dual / backward_dual); null without one
   class BatchNorm* dual_shortcut() const;
+  // GPU: the main path's closing LayerScale of an identity-shortcut block without activation: its
+  // store adds the block input, the first layer's data gradient adds the shortcut gradient
+  class LayerScale* scale_tail() const;
 
  private:
   std::vector<std::unique_ptr<Layer>> main_, short_;
@@ -554,6 +597,12 @@ class SequentialBuilder {
   SequentialBuilder& dense(int out_features, bool bias = true, const std::string& name = "");
   SequentialBuilder& groupnorm(int num_groups, float eps = 1e-5f, bool affine = true, const std::string& name = "");
   SequentialBuilder& dropout(float rate, const std::string& name = "");
+  SequentialBuilder& layernorm(float eps = 1e-6f, bool affine = true, const std::string& name = "");
+  SequentialBuilder& layer_scale(float init_value = 1e-6f, const std::string& name = "");
+  // ConvNeXt block: dw7x7 - LayerNorm - 1x1 (4x) - GELU - 1x1 - LayerScale, identity shortcut, no activation
+  SequentialBuilder& convnext_block(int channels, float layer_scale_init = 1e-6f, const std::string& name = "");
+  // ConvNeXt stage transition: LayerNorm (name_ln), then a 2x2 / stride-2 conv (name_conv)
+  SequentialBuilder& convnext_downsample(int out_ch, const std::string& name = "convnext_downsample");
   // generic residual block from prebuilt paths (shapes must agree)
   SequentialBuilder& residual(std::vector<std::unique_ptr<Layer>> main, std::vector<std::unique_ptr<Layer>> shortcut,
                               const std::string& activation = "relu", const std::string& name = "");

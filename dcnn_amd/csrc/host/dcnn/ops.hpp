@@ -13,7 +13,10 @@ struct ConvShape {
 struct PoolShape {
   int N, C, H, W, OH, OW, KH, KW, SH, SW, PH, PW;
 };
-enum ActKind { ACT_RELU = 0, ACT_LEAKY_RELU = 1, ACT_ELU = 2, ACT_SIGMOID = 3, ACT_TANH = 4, ACT_LINEAR = 5 };
+enum ActKind {
+  ACT_RELU = 0, ACT_LEAKY_RELU = 1, ACT_ELU = 2, ACT_SIGMOID = 3, ACT_TANH = 4, ACT_LINEAR = 5,
+  ACT_GELU = 6  // exact: x Phi(x)
+};
 
 namespace cpu_ops {
 void conv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s);
@@ -47,6 +50,15 @@ void groupnorm_fwd(const float* x, float* y, long N, long C, long HW, long G, co
                    float* smean, float* sistd);
 void groupnorm_bwd(const float* x, const float* dy, const float* mean, const float* istd, const float* g, float* dx,
                    float* dg, float* db, long N, long C, long HW, long G);
+// channel LayerNorm: every (n, position) of x [N][C][HW] over its C channels; statistics [N][HW];
+// g / b may be null (no affine), dg / db (+=) may be null
+void layernorm_fwd(const float* x, float* y, long N, long C, long HW, const float* g, const float* b, float eps,
+                   float* smean, float* srstd);
+void layernorm_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* g, float* dx,
+                   float* dg, float* db, long N, long C, long HW);
+// LayerScale: y = g[c] x (+ residual); dx = g[c] dy (may be null), dg += sum dy x
+void layer_scale_fwd(const float* x, const float* g, const float* residual, float* y, long N, long C, long HW);
+void layer_scale_bwd(const float* x, const float* dy, const float* g, float* dx, float* dg, long N, long C, long HW);
 void softmax_fwd(const float* x, float* y, long N, long C, long HW);
 void softmax_bwd(const float* y, const float* dy, float* dx, long N, long C, long HW);
 // inverted dropout with a counter-based mask of (seed, element index): the same call on dy
@@ -266,6 +278,16 @@ void groupnorm_fwd(const void* x, void* y, int N, int HW, int C, int G, const fl
                    float* smean, float* sistd);
 void groupnorm_bwd(const void* dy, const void* x, void* dx, int N, int HW, int C, int G, const float* g,
                    const float* mean, const float* istd, float* dg, float* db);
+// channel LayerNorm / LayerScale over bf16 NHWC rows [R][C] (lnorm.hip; R = N H W). Supported:
+// C % 8 == 0, 8 <= C <= 2048, R * C < 2^31: anything else throws std::runtime_error naming the
+// shape. g / b null: no affine; dg / db (+=) null: not computed. The backward passes' gradient
+// partials go through the library's grow-only workspace (no allocation once warmed up).
+void layernorm_fwd(const void* x, void* y, long R, int C, const float* g, const float* b, float eps, float* smean,
+                   float* srstd);
+void layernorm_bwd(const void* dy, const void* x, void* dx, long R, int C, const float* g, const float* mean,
+                   const float* rstd, float* dg, float* db);
+void layer_scale_fwd(const void* x, const float* g, const void* residual, void* y, long R, int C);
+void layer_scale_bwd(const void* dy, const void* x, const float* g, void* dx, float* dg, long R, int C);
 // softmax over the channels of every pixel (bf16 NHWC rows)
 void softmax_fwd(const void* x, void* y, long rows, int C);
 void softmax_bwd(const void* y, const void* dy, void* dx, long rows, int C);

@@ -62,6 +62,7 @@ int act_code(const std::string& k) {
   if (k == "sigmoid") return ACT_SIGMOID;
   if (k == "tanh") return ACT_TANH;
   if (k == "linear") return ACT_LINEAR;
+  if (k == "gelu") return ACT_GELU;
   throw std::invalid_argument("unknown activation '" + k + "'");
 }
 }  // namespace
@@ -371,6 +372,13 @@ json::Value GroupedConv2D::parameters_config() const {
   p["groups"] = g_;
   geometry_config(p);
   return p;
+}
+
+bool DepthwiseConv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
+  if (!dev_.is_gpu() || residual.shape() != mbc().a.shape())
+    throw std::runtime_error(name_ + ": backward_residual is a GPU fusion");
+  dx = backward_impl(dy, &residual);
+  return true;
 }
 
 bool GroupedConv2D::backward_residual(const Tensor& dy, const Tensor& residual, Tensor& dx) {
@@ -837,6 +845,7 @@ static int fuse_kind(const Layer* l) {
   if (auto* p = dynamic_cast<const Pool2D*>(l)) return p->is_max() ? FK_MAXPOOL : FK_AVGPOOL;
   if (dynamic_cast<const Flatten*>(l)) return FK_FLATTEN;
   if (dynamic_cast<const Dense*>(l)) return FK_DENSE;
+  if (dynamic_cast<const LayerScale*>(l)) return FK_LSCALE;
   return FK_OTHER;
 }
 
@@ -1003,6 +1012,118 @@ Tensor GroupNorm::backward(const Tensor& dy) {
   return dx;
 }
 
+// ------------------------------------------------------------------ LayerNorm (over channels)
+LayerNorm::LayerNorm(int num_channels, float eps, bool affine, std::string name)
+    : Layer(std::move(name)), c_(num_channels), eps_(eps), affine_(affine) {
+  if (c_ <= 0) throw std::invalid_argument("layernorm: num_channels must be positive");
+}
+
+json::Value LayerNorm::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["num_channels"] = c_;
+  p["epsilon"] = (double)eps_;
+  p["affine"] = affine_;
+  return p;
+}
+
+void LayerNorm::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+  (void)in;
+  (void)seed;
+  dev_ = dev;
+  params_.clear();
+  if (!affine_) return;
+  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f));
+  add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f));
+}
+
+Tensor LayerNorm::forward(const Tensor& x, bool training) {
+  (void)training;
+  MbCache& mc = mbc();
+  check_act(x, dev_, "layernorm");
+  if (x.dim(1) != c_) throw std::runtime_error(name_ + ": channel count mismatch");
+  const long N = x.dim(0), HW = x.dim(2) * x.dim(3);
+  mc.b.ensure({N * HW}, DType::F32, dev_);
+  mc.c.ensure({N * HW}, DType::F32, dev_);
+  const float* g = affine_ ? params_[0].value.ptr<float>() : nullptr;
+  const float* b = affine_ ? params_[1].value.ptr<float>() : nullptr;
+  Tensor y = act_empty(x.shape(), dev_);
+  if (dev_.is_gpu())
+    gpu_ops::layernorm_fwd(x.data(), y.data(), N * HW, c_, g, b, eps_, mc.b.ptr<float>(), mc.c.ptr<float>());
+  else
+    cpu_ops::layernorm_fwd(x.ptr<float>(), y.ptr<float>(), N, c_, HW, g, b, eps_, mc.b.ptr<float>(),
+                           mc.c.ptr<float>());
+  mc.a = x;
+  return y;
+}
+
+Tensor LayerNorm::backward(const Tensor& dy) {
+  MbCache& mc = mbc();
+  const Tensor& x_ = mc.a;
+  const long N = x_.dim(0), HW = x_.dim(2) * x_.dim(3);
+  Tensor dx = act_empty(x_.shape(), dev_);
+  const float* g = affine_ ? params_[0].value.ptr<float>() : nullptr;
+  float* dg = affine_ ? params_[0].grad.ptr<float>() : nullptr;
+  float* db = affine_ ? params_[1].grad.ptr<float>() : nullptr;
+  if (dev_.is_gpu())
+    gpu_ops::layernorm_bwd(dy.data(), x_.data(), dx.data(), N * HW, c_, g, mc.b.ptr<float>(), mc.c.ptr<float>(), dg,
+                           db);
+  else
+    cpu_ops::layernorm_bwd(x_.ptr<float>(), dy.ptr<float>(), mc.b.ptr<float>(), mc.c.ptr<float>(), g, dx.ptr<float>(),
+                           dg, db, N, c_, HW);
+  return dx;
+}
+
+// ------------------------------------------------------------------ LayerScale
+LayerScale::LayerScale(int num_channels, float init_value, std::string name)
+    : Layer(std::move(name)), c_(num_channels), init_(init_value) {
+  if (c_ <= 0) throw std::invalid_argument("layer_scale: num_channels must be positive");
+}
+
+json::Value LayerScale::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["num_channels"] = c_;
+  p["init_value"] = (double)init_;
+  return p;
+}
+
+void LayerScale::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+  (void)in;
+  (void)seed;
+  dev_ = dev;
+  params_.clear();
+  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, init_));
+}
+
+Tensor LayerScale::forward_residual(const Tensor& x, const Tensor* residual, bool training) {
+  (void)training;
+  check_act(x, dev_, "layer_scale");
+  if (x.dim(1) != c_) throw std::runtime_error(name_ + ": channel count mismatch");
+  if (residual != nullptr && residual->shape() != x.shape())
+    throw std::runtime_error(name_ + ": residual " + shape_str(residual->shape()) + " vs input " + shape_str(x.shape()));
+  const long N = x.dim(0), HW = x.dim(2) * x.dim(3);
+  const float* g = params_[0].value.ptr<float>();
+  Tensor y = act_empty(x.shape(), dev_);
+  if (dev_.is_gpu())
+    gpu_ops::layer_scale_fwd(x.data(), g, residual ? residual->data() : nullptr, y.data(), N * HW, c_);
+  else
+    cpu_ops::layer_scale_fwd(x.ptr<float>(), g, residual ? residual->ptr<float>() : nullptr, y.ptr<float>(), N, c_, HW);
+  mbc().a = x;
+  return y;
+}
+
+Tensor LayerScale::backward(const Tensor& dy) {
+  const Tensor& x_ = mbc().a;
+  const long N = x_.dim(0), HW = x_.dim(2) * x_.dim(3);
+  const float* g = params_[0].value.ptr<float>();
+  float* dg = params_[0].grad.ptr<float>();
+  Tensor dx = act_empty(x_.shape(), dev_);
+  if (dev_.is_gpu())
+    gpu_ops::layer_scale_bwd(dy.data(), x_.data(), g, dx.data(), dg, N * HW, c_);
+  else
+    cpu_ops::layer_scale_bwd(x_.ptr<float>(), dy.ptr<float>(), g, dx.ptr<float>(), dg, N, c_, HW);
+  return dx;
+}
+
 // ------------------------------------------------------------------ Dropout
 Dropout::Dropout(float rate, std::string name) : Layer(std::move(name)), p_(rate) {
   if (!(rate >= 0.f && rate < 1.f)) throw std::invalid_argument("dropout: rate must be in [0, 1)");
@@ -1145,9 +1266,24 @@ BatchNorm* ResidualBlock::fused_tail() const {
   return static_cast<BatchNorm*>(main_.back().get());
 }
 
+LayerScale* ResidualBlock::scale_tail() const {
+  if (!dev_.is_gpu() ||
+      !(plan_residual_fusions(fuse_kinds(main_), fuse_kinds(short_), act_ == "relu" || act_ == "linear",
+                              act_ == "none" || act_ == "linear") &
+        RF_SCALE_TAIL))
+    return nullptr;
+  return static_cast<LayerScale*>(main_.back().get());
+}
+
 Tensor ResidualBlock::forward(const Tensor& x, bool training) {
   check_act(x, dev_, "residual_block");
   Tensor& y_ = mbc().a;
+  if (LayerScale* ls = scale_tail()) {  // y = x + gamma main(x) in the LayerScale's store
+    Tensor m = x;
+    for (size_t i = 0; i + 1 < main_.size(); ++i) m = main_[i]->forward(m, training);
+    y_ = ls->forward_residual(m, &x, training);
+    return y_;
+  }
   if (BatchNorm* tail = fused_tail()) {  // y = act(bn(main(x)) + shortcut(x)) in the BN's apply pass
     // a projection shortcut's closing BatchNorm is applied inside the same pass (forward_dual):
     // its statistics rows are taken now (the shortcut conv's slab in the secondary workspace, so
@@ -1185,6 +1321,19 @@ Tensor ResidualBlock::forward(const Tensor& x, bool training) {
 
 Tensor ResidualBlock::backward(const Tensor& dy) {
   const Tensor& y_ = mbc().a;
+  if (scale_tail() != nullptr) {
+    // the shortcut gradient is dy itself: the first layer's data gradient adds it in its store
+    Tensor gm = dy;
+    for (size_t i = main_.size(); i-- > 1;) gm = main_[i]->backward(gm);
+    auto* head = dynamic_cast<ConvBase*>(main_[0].get());
+    Tensor dx;
+    if (head != nullptr && input_grad_ && head->backward_residual(gm, dy, dx)) return dx;
+    gm = main_[0]->backward(gm);
+    if (!gm.defined()) return Tensor();
+    dx = act_empty(gm.shape(), dev_);
+    gpu_ops::add(gm.data(), dy.data(), dx.data(), dx.numel(), false);
+    return dx;
+  }
   if (BatchNorm* tail = fused_tail()) {
     Tensor gs, gm;  // gs: the activation-masked dy, for the shortcut
     BatchNorm* sbn = dual_shortcut();
@@ -1443,6 +1592,11 @@ std::unique_ptr<Layer> create_layer(const json::Value& rec) {
   if (type == "groupnorm")
     return std::make_unique<GroupNorm>(I("num_groups", 1), I("num_channels", 0), (float)p.get_number("epsilon", 1e-5),
                                        p.get_bool("affine", true), name);
+  if (type == "layernorm")
+    return std::make_unique<LayerNorm>(I("num_channels", 0), (float)p.get_number("epsilon", 1e-6),
+                                       p.get_bool("affine", true), name);
+  if (type == "layer_scale")
+    return std::make_unique<LayerScale>(I("num_channels", 0), (float)p.get_number("init_value", 1e-6), name);
   if (type == "dropout") return std::make_unique<Dropout>((float)p.get_number("dropout_rate", 0.5), name);
   if (type == "residual_block") {
     auto path = [&](const char* key) {
@@ -1867,6 +2021,35 @@ SequentialBuilder& SequentialBuilder::dense(int out_features, bool bias, const s
 SequentialBuilder& SequentialBuilder::groupnorm(int num_groups, float eps, bool affine, const std::string& name) {
   model_.add(std::make_unique<GroupNorm>(num_groups, (int)cur_.at(0), eps, affine, auto_name(name, "groupnorm")));
   return *this;
+}
+
+SequentialBuilder& SequentialBuilder::layernorm(float eps, bool affine, const std::string& name) {
+  model_.add(std::make_unique<LayerNorm>((int)cur_.at(0), eps, affine, auto_name(name, "layernorm")));
+  return *this;
+}
+
+SequentialBuilder& SequentialBuilder::layer_scale(float init_value, const std::string& name) {
+  model_.add(std::make_unique<LayerScale>((int)cur_.at(0), init_value, auto_name(name, "layer_scale")));
+  return *this;
+}
+
+// (sub-layer names as the Python LayerBuilder numbers them)
+SequentialBuilder& SequentialBuilder::convnext_block(int channels, float layer_scale_init, const std::string& name) {
+  if (channels != conv_in()) throw std::invalid_argument("convnext_block: channels must match the running shape");
+  std::vector<std::unique_ptr<Layer>> m, sc;
+  m.push_back(std::make_unique<DepthwiseConv2D>(channels, 7, 7, 1, 1, 3, 3, true, "depthwise_conv2d_0"));
+  m.push_back(std::make_unique<LayerNorm>(channels, 1e-6f, true, "layernorm_1"));
+  m.push_back(std::make_unique<Conv2D>(channels, 4 * channels, 1, 1, 1, 1, 0, 0, true, "conv2d_2"));
+  m.push_back(std::make_unique<Activation>("gelu", "activation_3"));
+  m.push_back(std::make_unique<Conv2D>(4 * channels, channels, 1, 1, 1, 1, 0, 0, true, "conv2d_4"));
+  m.push_back(std::make_unique<LayerScale>(channels, layer_scale_init, "layer_scale_5"));
+  return residual(std::move(m), std::move(sc), "none",
+                  name.empty() ? "convnext_block_" + std::to_string(model_.layers().size()) : name);
+}
+
+SequentialBuilder& SequentialBuilder::convnext_downsample(int out_ch, const std::string& name) {
+  layernorm(1e-6f, true, name + "_ln");
+  return conv2d(out_ch, 2, 2, 2, 2, 0, 0, true, name + "_conv");
 }
 
 SequentialBuilder& SequentialBuilder::dropout(float rate, const std::string& name) {

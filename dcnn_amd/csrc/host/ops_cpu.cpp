@@ -69,9 +69,10 @@ void avgpool_bwd(const float* dy, float* dx, const PoolShape& p) {
   C::avgpool_bwd(dy, dx, (long)p.N * p.C, p.H, p.W, p.KH, p.KW, p.SH, p.SW, p.PH, p.PW);
 }
 
-// the CPU kernels number activations 0 linear, 1 relu, 2 leaky, 3 elu, 4 sigmoid, 5 tanh
+// the CPU kernels number activations 0 linear, 1 relu, 2 leaky, 3 elu, 4 sigmoid, 5 tanh, 6 gelu
 static int cpu_act(int kind) {
-  static const int map[] = {1, 2, 3, 4, 5, 0};
+  static const int map[] = {1, 2, 3, 4, 5, 0, 6};
+  if (kind < 0 || kind > 6) throw std::invalid_argument("activation: unknown kind");
   return map[kind];
 }
 
@@ -101,6 +102,24 @@ void groupnorm_fwd(const float* x, float* y, long N, long Cc, long HW, long G, c
 void groupnorm_bwd(const float* x, const float* dy, const float* mean, const float* istd, const float* g, float* dx,
                    float* dg, float* db, long N, long Cc, long HW, long G) {
   C::groupnorm_bwd<float>(x, dy, mean, istd, g, dx, dg, db, N, Cc, HW, G);
+}
+
+void layernorm_fwd(const float* x, float* y, long N, long Cc, long HW, const float* g, const float* b, float eps,
+                   float* smean, float* srstd) {
+  C::layernorm_fwd<float>(x, y, N, Cc, HW, g, b, eps, smean, srstd);
+}
+
+void layernorm_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* g, float* dx,
+                   float* dg, float* db, long N, long Cc, long HW) {
+  C::layernorm_bwd<float>(x, dy, mean, rstd, g, dx, dg, db, N, Cc, HW);
+}
+
+void layer_scale_fwd(const float* x, const float* g, const float* residual, float* y, long N, long Cc, long HW) {
+  C::layer_scale_fwd<float>(x, g, residual, y, N, Cc, HW);
+}
+
+void layer_scale_bwd(const float* x, const float* dy, const float* g, float* dx, float* dg, long N, long Cc, long HW) {
+  C::layer_scale_bwd<float>(x, dy, g, dx, dg, N, Cc, HW);
 }
 
 void softmax_fwd(const float* x, float* y, long N, long Cc, long HW) { C::softmax_channels<float>(x, y, N, Cc, HW); }

@@ -344,7 +344,7 @@ inline hipStream_t cur() { return static_cast<hipStream_t>(gpu::flow()); }
 
 // grow-only workspace per purpose
 enum Slot { W_T = 0, SLAB, BSLAB, STAT_SLAB, STAT_SUMS, STAT_PART, LOSS_WS, LOSS_OUT, TICKETS, HPART, HTICKETS, GN_AFF,
-            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, NSLOTS };
+            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, LN_WS, NSLOTS };
 void* scratch(Slot s, size_t bytes) {
   static void* p[NSLOTS] = {};
   static size_t n[NSLOTS] = {};
@@ -1136,6 +1136,37 @@ void groupnorm_bwd(const void* dy, const void* x, void* dx, int N, int HW, int C
                    const float* mean, const float* istd, float* dg, float* db) {
   float* aff = static_cast<float*>(scratch(GN_AFF, (size_t)N * 2 * C * 4));  // per-image affine partials
   gn_bwd(kBF16, dy, x, dx, N, HW, C, G, g, mean, istd, dg, db, aff, cur());
+}
+
+// ---- channel LayerNorm / LayerScale (lnorm.hip)
+static void ln_check(const char* what, long R, int C) {
+  if (!ln_supported(kBF16, R, C))
+    throw std::runtime_error(std::string(what) + ": unsupported shape: " + std::to_string(R) + " rows of C " +
+                             std::to_string(C) + " channels (bf16 needs C % 8 == 0, 8 <= C <= 2048, R * C < 2^31)");
+}
+
+void layernorm_fwd(const void* x, void* y, long R, int C, const float* g, const float* b, float eps, float* smean,
+                   float* srstd) {
+  ln_check("layernorm_fwd", R, C);
+  ln_fwd(kBF16, x, y, R, C, g, b, eps, smean, srstd, cur());
+}
+
+void layernorm_bwd(const void* dy, const void* x, void* dx, long R, int C, const float* g, const float* mean,
+                   const float* rstd, float* dg, float* db) {
+  ln_check("layernorm_bwd", R, C);
+  float* ws = dg || db ? static_cast<float*>(scratch(LN_WS, (size_t)ln_workspace_bytes(R, C))) : nullptr;
+  ln_bwd(kBF16, dy, x, dx, R, C, g, mean, rstd, dg, db, ws, cur());
+}
+
+void layer_scale_fwd(const void* x, const float* g, const void* residual, void* y, long R, int C) {
+  ln_check("layer_scale_fwd", R, C);
+  lscale_fwd(kBF16, x, g, residual, y, R, C, cur());
+}
+
+void layer_scale_bwd(const void* dy, const void* x, const float* g, void* dx, float* dg, long R, int C) {
+  ln_check("layer_scale_bwd", R, C);
+  float* ws = static_cast<float*>(scratch(LN_WS, (size_t)ln_workspace_bytes(R, C)));
+  lscale_bwd(kBF16, dy, x, g, dx, dg, R, C, ws, cur());
 }
 
 void softmax_fwd(const void* x, void* y, long rows, int C) { softmax_rows(kBF16, x, y, rows, C, cur()); }

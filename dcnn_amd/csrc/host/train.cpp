@@ -675,6 +675,30 @@ Sequential create_model(const std::string& name) {
       }
     return b.avgpool2d(4, 4, 1, 1, 0, 0, "avgpool").flatten("flatten").dense(tiny ? 200 : 10, true, "fc").build();
   }
+  if (name == "convnext_pico_cifar10" || name == "convnext_tiny_tiny_imagenet") {
+    // ConvNeXt (models/zoo.py _convnext: same layer names and order): patchify stem + LayerNorm,
+    // four stages of ConvNeXt blocks with LayerNorm + 2x2 / stride-2 transitions, pool - LayerNorm - fc
+    const bool tiny = name == "convnext_tiny_tiny_imagenet";
+    const int patch = tiny ? 4 : 2, hw = tiny ? 64 : 32;
+    const int depthsT[4] = {3, 3, 9, 3}, depthsP[4] = {2, 2, 6, 2};
+    const int widthsT[4] = {96, 192, 384, 768}, widthsP[4] = {64, 128, 256, 512};
+    const int* depths = tiny ? depthsT : depthsP;
+    const int* widths = tiny ? widthsT : widthsP;
+    SequentialBuilder b(tiny ? "ConvNeXt-T-Tiny-ImageNet" : "ConvNeXt-Pico-CIFAR10");
+    b.input({3, hw, hw}).conv2d(widths[0], patch, patch, patch, patch, 0, 0, true, "stem_conv")
+        .layernorm(1e-6f, true, "stem_ln");
+    int m = hw / patch;
+    for (int s = 0; s < 4; ++s) {
+      if (s > 0) {
+        b.convnext_downsample(widths[s], "down" + std::to_string(s + 1));
+        m /= 2;
+      }
+      for (int i = 1; i <= depths[s]; ++i)
+        b.convnext_block(widths[s], 1e-6f, "stage" + std::to_string(s + 1) + "_block" + std::to_string(i));
+    }
+    return b.avgpool2d(m, m, 1, 1, 0, 0, "avgpool").layernorm(1e-6f, true, "head_ln").flatten("flatten")
+        .dense(tiny ? 200 : 10, true, "fc").build();
+  }
   throw std::invalid_argument("unknown model '" + name + "'");
 }
 

@@ -272,6 +272,26 @@ void gn_fwd(int dtype, const void* x, void* y, int N, int HW, int C, int G, cons
             float eps, float* save_mean, float* save_istd, hipStream_t s);
 void gn_bwd(int dtype, const void* dy, const void* x, void* dx, int N, int HW, int C, int G, const float* gamma,
             const float* mean, const float* istd, float* dgamma, float* dbeta, float* aff, hipStream_t s);
+// Channel LayerNorm / LayerScale (lnorm.hip) over R = N H W rows of C contiguous channels; dt 0
+// fp32 / 1 bf16 I/O, fp32 arithmetic, parameters and gradients. Supported: C % 4 (fp32) / % 8
+// (bf16) == 0, 8 <= C <= 2048, R * C < 2^31; the launchers throw std::invalid_argument on
+// anything else. The backward passes write per-workgroup gradient partials into `workspace`
+// (ln_workspace_bytes; ln_partial_rows slab rows) and ADD their fixed-order sum to the gradients.
+bool ln_supported(int dt, long R, int C);
+int ln_partial_rows(long R, int C);
+long ln_workspace_bytes(long R, int C);
+// y = (x - mean) rstd gamma + beta per row (gamma / beta null: no affine); saves mean, rstd [R]
+void ln_fwd(int dt, const void* x, void* y, long R, int C, const float* gamma, const float* beta, float eps,
+            float* save_mean, float* save_rstd, hipStream_t s);
+// dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy gamma; dgamma += sum dy xhat, dbeta += sum dy
+void ln_bwd(int dt, const void* dy, const void* x, void* dx, long R, int C, const float* gamma, const float* mean,
+            const float* rstd, float* dgamma, float* dbeta, float* workspace, hipStream_t s);
+// y = gamma[c] x (+ residual, a same-shape activation)
+void lscale_fwd(int dt, const void* x, const float* gamma, const void* residual, void* y, long R, int C,
+                hipStream_t s);
+// dx = gamma[c] dy; dgamma += sum dy x
+void lscale_bwd(int dt, const void* dy, const void* x, const float* gamma, void* dx, float* dgamma, long R, int C,
+                float* workspace, hipStream_t s);
 
 void maxpool_fwd(int dt, const void* x, void* y, uint8_t* idx, PoolGeom g, hipStream_t s);
 void maxpool_bwd(int dt, const void* dy, const uint8_t* idx, void* dx, PoolGeom g, hipStream_t s);

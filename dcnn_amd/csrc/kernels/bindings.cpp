@@ -245,7 +245,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("ROUTE_HALO_S2") = (int)ROUTE_HALO_S2;
   // the shared fusion planner (fusion_plan.cpp)
   m.def("plan_sequence_fusions", &plan_sequence_fusions);
-  m.def("plan_residual_fusions", &plan_residual_fusions);
+  m.def("plan_residual_fusions", &plan_residual_fusions, py::arg("main_kinds"), py::arg("short_kinds"),
+        py::arg("act_ok"), py::arg("act_identity") = false);
   for (auto [name, v] : {std::pair<const char*, int>{"FK_OTHER", FK_OTHER}, {"FK_CONV", FK_CONV}, {"FK_BN", FK_BN},
                          {"FK_RELU", FK_RELU}, {"FK_ACT", FK_ACT}, {"FK_MAXPOOL", FK_MAXPOOL},
                          {"FF_EMIT_BN_STATS", FF_EMIT_BN_STATS}, {"FF_FUSE_RELU", FF_FUSE_RELU},
@@ -253,7 +254,8 @@ PYBIND11_MODULE(_kernels, m) {
                          {"FF_BNB_CONSUMER", FF_BNB_CONSUMER}, {"FK_AVGPOOL", FK_AVGPOOL},
                          {"FK_FLATTEN", FK_FLATTEN}, {"FK_DENSE", FK_DENSE}, {"FF_FUSE_HEAD", FF_FUSE_HEAD},
                          {"RF_FUSED_TAIL", RF_FUSED_TAIL},
-                         {"RF_DUAL_SHORTCUT", RF_DUAL_SHORTCUT}})
+                         {"RF_DUAL_SHORTCUT", RF_DUAL_SHORTCUT}, {"FK_LSCALE", FK_LSCALE},
+                         {"RF_SCALE_TAIL", RF_SCALE_TAIL}})
     m.attr(name) = v;
   m.def("g1s_rows", &g1s_rows);
   m.def("g1s_enable", &g1s_enable);
@@ -373,6 +375,29 @@ PYBIND11_MODULE(_kernels, m) {
                      uintptr_t mean, uintptr_t istd, uintptr_t dg, uintptr_t db, uintptr_t aff, uintptr_t st) {
     gn_bwd(dt, P<const void*>(dy), P<const void*>(x), P<void*>(dx), N, HW, C, G, P<const float*>(gamma),
            P<const float*>(mean), P<const float*>(istd), P<float*>(dg), P<float*>(db), P<float*>(aff), S(st));
+  });
+  // channel LayerNorm / LayerScale (lnorm.hip)
+  m.def("ln_supported", &ln_supported);
+  m.def("ln_partial_rows", &ln_partial_rows);
+  m.def("ln_workspace_bytes", &ln_workspace_bytes);
+  m.def("ln_fwd", [](int dt, uintptr_t x, uintptr_t y, long R, int C, uintptr_t gamma, uintptr_t beta, float eps,
+                     uintptr_t sm, uintptr_t sr, uintptr_t st) {
+    ln_fwd(dt, P<const void*>(x), P<void*>(y), R, C, P<const float*>(gamma), P<const float*>(beta), eps,
+           P<float*>(sm), P<float*>(sr), S(st));
+  });
+  m.def("ln_bwd", [](int dt, uintptr_t dy, uintptr_t x, uintptr_t dx, long R, int C, uintptr_t gamma, uintptr_t mean,
+                     uintptr_t rstd, uintptr_t dg, uintptr_t db, uintptr_t ws, uintptr_t st) {
+    ln_bwd(dt, P<const void*>(dy), P<const void*>(x), P<void*>(dx), R, C, P<const float*>(gamma),
+           P<const float*>(mean), P<const float*>(rstd), P<float*>(dg), P<float*>(db), P<float*>(ws), S(st));
+  });
+  m.def("lscale_fwd", [](int dt, uintptr_t x, uintptr_t gamma, uintptr_t residual, uintptr_t y, long R, int C,
+                         uintptr_t st) {
+    lscale_fwd(dt, P<const void*>(x), P<const float*>(gamma), P<const void*>(residual), P<void*>(y), R, C, S(st));
+  });
+  m.def("lscale_bwd", [](int dt, uintptr_t dy, uintptr_t x, uintptr_t gamma, uintptr_t dx, uintptr_t dg, long R, int C,
+                         uintptr_t ws, uintptr_t st) {
+    lscale_bwd(dt, P<const void*>(dy), P<const void*>(x), P<const float*>(gamma), P<void*>(dx), P<float*>(dg), R, C,
+               P<float*>(ws), S(st));
   });
 
   // depthwise conv (dwconv.hip): geometry as (N, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW)

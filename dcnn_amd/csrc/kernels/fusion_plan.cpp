@@ -37,7 +37,11 @@ std::vector<int> plan_sequence_fusions(const std::vector<int>& kinds) {
   return f;
 }
 
-int plan_residual_fusions(const std::vector<int>& main_kinds, const std::vector<int>& short_kinds, bool act_ok) {
+int plan_residual_fusions(const std::vector<int>& main_kinds, const std::vector<int>& short_kinds, bool act_ok,
+                          bool act_identity) {
+  // identity shortcut, no activation, main path closing in a LayerScale: x + gamma F(x) in its store
+  if (act_identity && short_kinds.empty() && main_kinds.size() >= 2 && main_kinds.back() == FK_LSCALE)
+    return RF_SCALE_TAIL;
   // the main path's closing BatchNorm applies the shortcut sum and the block activation
   const bool tail = act_ok && main_kinds.size() >= 2 && main_kinds.back() == FK_BN;
   if (!tail) return 0;

@@ -410,7 +410,7 @@ __global__ void global_avgpool_bwd_kernel(const T* __restrict__ dy, T* __restric
 }
 
 // ----------------------------------- activations -----------------------------------------
-enum Act { kRelu = 0, kLeaky = 1, kElu = 2, kSigmoid = 3, kTanh = 4, kLinear = 5 };
+enum Act { kRelu = 0, kLeaky = 1, kElu = 2, kSigmoid = 3, kTanh = 4, kLinear = 5, kGelu = 6 };
 
 __device__ __forceinline__ float act_f(int t, float x, float a) {
   switch (t) {
@@ -419,6 +419,7 @@ __device__ __forceinline__ float act_f(int t, float x, float a) {
     case kElu: return x > 0.f ? x : a * (__expf(x) - 1.f);
     case kSigmoid: return 1.f / (1.f + __expf(-x));
     case kTanh: return tanhf(x);
+    case kGelu: return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));  // exact form x Phi(x)
     default: return x;
   }
 }
@@ -429,6 +430,8 @@ __device__ __forceinline__ float act_df(int t, float x, float a) {
     case kElu: return x > 0.f ? 1.f : a * __expf(x);
     case kSigmoid: { const float s = 1.f / (1.f + __expf(-x)); return s * (1.f - s); }
     case kTanh: { const float t2 = tanhf(x); return 1.f - t2 * t2; }
+    case kGelu:  // Phi(x) + x phi(x)
+      return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
     default: return 1.f;
   }
 }

@@ -142,6 +142,25 @@ void bind_cpu(py::module_& parent) {
     DT_DISPATCH(dt, groupnorm_bwd<T>(P<const T>(x), P<const T>(dy), P<const T>(mean), P<const T>(istd),
                                      P<const T>(gamma), P<T>(dx), P<T>(dgamma), P<T>(dbeta), N, C, HW, G));
   }, Rel());
+  m.def("layernorm_fwd", [](int dt, uintptr_t x, uintptr_t y, long N, long C, long HW, uintptr_t gamma,
+                            uintptr_t beta, double eps, uintptr_t smean, uintptr_t srstd) {
+    DT_DISPATCH(dt, layernorm_fwd<T>(P<const T>(x), P<T>(y), N, C, HW, P<const T>(gamma), P<const T>(beta), eps,
+                                     P<T>(smean), P<T>(srstd)));
+  }, Rel());
+  m.def("layernorm_bwd", [](int dt, uintptr_t x, uintptr_t dy, uintptr_t mean, uintptr_t rstd, uintptr_t gamma,
+                            uintptr_t dx, uintptr_t dgamma, uintptr_t dbeta, long N, long C, long HW) {
+    DT_DISPATCH(dt, layernorm_bwd<T>(P<const T>(x), P<const T>(dy), P<const T>(mean), P<const T>(rstd),
+                                     P<const T>(gamma), P<T>(dx), P<T>(dgamma), P<T>(dbeta), N, C, HW));
+  }, Rel());
+  m.def("layer_scale_fwd", [](int dt, uintptr_t x, uintptr_t gamma, uintptr_t residual, uintptr_t y, long N, long C,
+                              long HW) {
+    DT_DISPATCH(dt, layer_scale_fwd<T>(P<const T>(x), P<const T>(gamma), P<const T>(residual), P<T>(y), N, C, HW));
+  }, Rel());
+  m.def("layer_scale_bwd", [](int dt, uintptr_t x, uintptr_t dy, uintptr_t gamma, uintptr_t dx, uintptr_t dgamma,
+                              long N, long C, long HW) {
+    DT_DISPATCH(dt, layer_scale_bwd<T>(P<const T>(x), P<const T>(dy), P<const T>(gamma), P<T>(dx), P<T>(dgamma), N, C,
+                                       HW));
+  }, Rel());
   m.def("maxpool_fwd", [](int dt, uintptr_t x, uintptr_t y, uintptr_t idx, long NC, int H, int W, int KH, int KW,
                           int SH, int SW, int PH, int PW) {
     DT_DISPATCH(dt, maxpool_fwd<T>(P<const T>(x), P<T>(y), P<int32_t>(idx), NC, H, W, KH, KW, SH, SW, PH, PW));

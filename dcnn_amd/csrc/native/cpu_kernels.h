@@ -66,6 +66,18 @@ void groupnorm_fwd(const T* x, T* y, long N, long C, long HW, long G, const T* g
 template <typename T>
 void groupnorm_bwd(const T* x, const T* dy, const T* mean, const T* istd, const T* gamma, T* dx, T* dgamma, T* dbeta,
                    long N, long C, long HW, long G);
+// channel LayerNorm: every (n, position) over its C channels; statistics [N][HW]; dgamma / dbeta +=
+template <typename T>
+void layernorm_fwd(const T* x, T* y, long N, long C, long HW, const T* gamma, const T* beta, double eps, T* save_mean,
+                   T* save_rstd);
+template <typename T>
+void layernorm_bwd(const T* x, const T* dy, const T* mean, const T* rstd, const T* gamma, T* dx, T* dgamma, T* dbeta,
+                   long N, long C, long HW);
+// y = gamma[c] x (+ residual); dx = gamma[c] dy (may be null), dgamma += (may be null)
+template <typename T>
+void layer_scale_fwd(const T* x, const T* gamma, const T* residual, T* y, long N, long C, long HW);
+template <typename T>
+void layer_scale_bwd(const T* x, const T* dy, const T* gamma, T* dx, T* dgamma, long N, long C, long HW);
 template <typename T>
 void maxpool_fwd(const T* x, T* y, int32_t* idx, long NC, int H, int W, int KH, int KW, int SH, int SW, int PH, int PW);
 template <typename T> void maxpool_bwd(const T* dy, const int32_t* idx, T* dx, long NC, int H, int W, int OH, int OW);

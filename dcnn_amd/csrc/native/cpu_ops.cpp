@@ -874,6 +874,133 @@ void groupnorm_bwd(const T* x, const T* dy, const T* mean, const T* istd, const 
   });
 }
 
+// ------------------------------------------------------------------ channel layer norm
+// Normalises every (n, spatial) position over its C channels: x [N][C][HW], statistics [N][HW].
+// Sums run over c in ascending order in double (dgamma / dbeta: over n, then the position), so
+// the result does not depend on the thread count.
+template <typename T>
+void layernorm_fwd(const T* x, T* y, long N, long C, long HW, const T* gamma, const T* beta, double eps, T* save_mean,
+                   T* save_rstd) {
+  parallel_for(0, N, 1, [&](long lo, long hi) {
+    std::vector<double> mean(HW), rstd(HW);
+    for (long n = lo; n < hi; ++n) {
+      const T* r = x + n * C * HW;
+      std::fill(mean.begin(), mean.end(), 0.0);
+      std::fill(rstd.begin(), rstd.end(), 0.0);
+      for (long c = 0; c < C; ++c)
+        for (long i = 0; i < HW; ++i) mean[i] += r[c * HW + i];
+      for (long i = 0; i < HW; ++i) mean[i] /= (double)C;
+      for (long c = 0; c < C; ++c)
+        for (long i = 0; i < HW; ++i) {
+          const double d = r[c * HW + i] - mean[i];
+          rstd[i] += d * d;  // the centred sum of squares until the loop below
+        }
+      for (long i = 0; i < HW; ++i) {
+        rstd[i] = 1.0 / std::sqrt(rstd[i] / (double)C + eps);
+        save_mean[n * HW + i] = (T)mean[i];
+        save_rstd[n * HW + i] = (T)rstd[i];
+      }
+      T* o = y + n * C * HW;
+      for (long c = 0; c < C; ++c) {
+        const double ga = gamma ? (double)gamma[c] : 1.0, be = beta ? (double)beta[c] : 0.0;
+        for (long i = 0; i < HW; ++i) o[c * HW + i] = (T)((r[c * HW + i] - mean[i]) * rstd[i] * ga + be);
+      }
+    }
+  });
+}
+
+template <typename T>
+void layernorm_bwd(const T* x, const T* dy, const T* mean, const T* rstd, const T* gamma, T* dx, T* dgamma, T* dbeta,
+                   long N, long C, long HW) {
+  if (dgamma || dbeta)
+    parallel_for(0, C, 1, [&](long lo, long hi) {
+      for (long c = lo; c < hi; ++c) {
+        double sg = 0.0, sb = 0.0;
+        for (long n = 0; n < N; ++n) {
+          const T* d = dy + (n * C + c) * HW;
+          const T* xr = x + (n * C + c) * HW;
+          for (long i = 0; i < HW; ++i) {
+            sb += d[i];
+            sg += (double)d[i] * (((double)xr[i] - mean[n * HW + i]) * rstd[n * HW + i]);
+          }
+        }
+        if (dgamma) dgamma[c] += (T)sg;
+        if (dbeta) dbeta[c] += (T)sb;
+      }
+    });
+  parallel_for(0, N, 1, [&](long lo, long hi) {
+    std::vector<double> m1(HW), m2(HW);
+    for (long n = lo; n < hi; ++n) {
+      const long base = n * C * HW;
+      std::fill(m1.begin(), m1.end(), 0.0);
+      std::fill(m2.begin(), m2.end(), 0.0);
+      for (long c = 0; c < C; ++c) {
+        const double ga = gamma ? (double)gamma[c] : 1.0;
+        for (long i = 0; i < HW; ++i) {
+          const long k = base + c * HW + i;
+          const double d = dy[k] * ga;
+          m1[i] += d;
+          m2[i] += d * (((double)x[k] - mean[n * HW + i]) * rstd[n * HW + i]);
+        }
+      }
+      for (long i = 0; i < HW; ++i) {
+        m1[i] /= (double)C;
+        m2[i] /= (double)C;
+      }
+      for (long c = 0; c < C; ++c) {
+        const double ga = gamma ? (double)gamma[c] : 1.0;
+        for (long i = 0; i < HW; ++i) {
+          const long k = base + c * HW + i;
+          const double is = rstd[n * HW + i], xh = ((double)x[k] - mean[n * HW + i]) * is;
+          dx[k] = (T)(is * (dy[k] * ga - m1[i] - xh * m2[i]));
+        }
+      }
+    }
+  });
+}
+
+// ------------------------------------------------------------------ layer scale
+// y = gamma[c] x (+ residual); dx = gamma[c] dy, dgamma[c] += sum over (n, position) of dy x
+template <typename T>
+void layer_scale_fwd(const T* x, const T* gamma, const T* residual, T* y, long N, long C, long HW) {
+  parallel_for(0, N * C, 1, [&](long lo, long hi) {
+    for (long p = lo; p < hi; ++p) {
+      const T g = gamma[p % C];
+      const T* r = x + p * HW;
+      T* o = y + p * HW;
+      if (residual) {
+        const T* s = residual + p * HW;
+        for (long i = 0; i < HW; ++i) o[i] = g * r[i] + s[i];
+      } else {
+        for (long i = 0; i < HW; ++i) o[i] = g * r[i];
+      }
+    }
+  });
+}
+
+template <typename T>
+void layer_scale_bwd(const T* x, const T* dy, const T* gamma, T* dx, T* dgamma, long N, long C, long HW) {
+  if (dgamma)
+    parallel_for(0, C, 1, [&](long lo, long hi) {
+      for (long c = lo; c < hi; ++c) {
+        double s = 0.0;
+        for (long n = 0; n < N; ++n) {
+          const T* d = dy + (n * C + c) * HW;
+          const T* xr = x + (n * C + c) * HW;
+          for (long i = 0; i < HW; ++i) s += (double)d[i] * xr[i];
+        }
+        dgamma[c] += (T)s;
+      }
+    });
+  if (dx)
+    parallel_for(0, N * C, 1, [&](long lo, long hi) {
+      for (long p = lo; p < hi; ++p) {
+        const T g = gamma[p % C];
+        for (long i = 0; i < HW; ++i) dx[p * HW + i] = g * dy[p * HW + i];
+      }
+    });
+}
+
 // ------------------------------------------------------------------ pooling
 // argmax index = iy * W + ix within the plane (first maximum in window order), -1 for an
 // all-padding window
@@ -974,11 +1101,12 @@ void avgpool_bwd(const T* dy, T* dx, long NC, int H, int W, int KH, int KW, int 
 }
 
 // ------------------------------------------------------------------ activations
-// type: 0 linear, 1 relu, 2 leaky_relu(alpha), 3 elu(alpha), 4 sigmoid, 5 tanh
+// type: 0 linear, 1 relu, 2 leaky_relu(alpha), 3 elu(alpha), 4 sigmoid, 5 tanh, 6 gelu (exact: x Phi(x))
 template <typename T>
 void act_fwd(int type, const T* x, T* y, long n, double alpha) {
   const T a = (T)alpha;
   switch (type) {
+    case 6: return map1(x, y, n, [](T v) { return T(0.5) * v * (T(1) + std::erf(v * T(0.70710678118654752440))); });
     case 1: return map1(x, y, n, [](T v) { return v > T(0) ? v : T(0); });
     case 2: return map1(x, y, n, [&](T v) { return v > T(0) ? v : v * a; });
     case 3: return map1(x, y, n, [&](T v) { return v > T(0) ? v : a * (std::exp(v) - T(1)); });
@@ -1002,6 +1130,10 @@ void act_bwd(int type, const T* x, const T* dy, T* dx, long n, double alpha) {
     case 5: return map2(x, dy, dx, n, [](T v, T g) {
       const T t = std::tanh(v);
       return g * (T(1) - t * t);
+    });
+    case 6: return map2(x, dy, dx, n, [](T v, T g) {  // Phi(x) + x phi(x)
+      const T cdf = T(0.5) * (T(1) + std::erf(v * T(0.70710678118654752440)));
+      return g * (cdf + v * T(0.39894228040143267794) * std::exp(T(-0.5) * v * v));
     });
     default: return map2(x, dy, dx, n, [](T, T g) { return g; });
   }
@@ -1179,6 +1311,10 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
   template void groupnorm_fwd<T>(const T*, T*, long, long, long, long, const T*, const T*, double, T*, T*);          \
   template void groupnorm_bwd<T>(const T*, const T*, const T*, const T*, const T*, T*, T*, T*, long, long, long,     \
                                  long);                                                                             \
+  template void layernorm_fwd<T>(const T*, T*, long, long, long, const T*, const T*, double, T*, T*);                \
+  template void layernorm_bwd<T>(const T*, const T*, const T*, const T*, const T*, T*, T*, T*, long, long, long);    \
+  template void layer_scale_fwd<T>(const T*, const T*, const T*, T*, long, long, long);                             \
+  template void layer_scale_bwd<T>(const T*, const T*, const T*, T*, T*, long, long, long);                         \
   template void maxpool_fwd<T>(const T*, T*, int32_t*, long, int, int, int, int, int, int, int, int);               \
   template void maxpool_bwd<T>(const T*, const int32_t*, T*, long, int, int, int, int);                             \
   template void avgpool_fwd<T>(const T*, T*, long, int, int, int, int, int, int, int, int);                         \

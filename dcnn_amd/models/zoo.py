@@ -233,6 +233,30 @@ def create_resnext26_32x4d_cifar10() -> Sequential:
             .dense(10, True, "fc").build())
 
 
+def _convnext(name, hw, patch, depths, widths, classes) -> Sequential:
+    """ConvNeXt (Liu et al. 2022): a patchify stem (patch x patch conv, stride = patch) + LayerNorm,
+    four stages of ConvNeXt blocks with LayerNorm + 2x2 / stride-2 conv transitions, then average
+    pool -> LayerNorm -> dense. Every bias is on; no stochastic depth."""
+    b = (SequentialBuilder(name).input([3, hw, hw])
+         .conv2d(widths[0], patch, patch, patch, patch, 0, 0, True, "stem_conv").layernorm(1e-6, True, "stem_ln"))
+    for s, (n, w) in enumerate(zip(depths, widths), 1):
+        if s > 1:
+            b.convnext_downsample(w, f"down{s}")
+        for i in range(1, n + 1):
+            b.convnext_block(w, 1e-6, f"stage{s}_block{i}")
+    m = b.get_current_shape()[2]
+    return (b.avgpool2d(m, m, 1, 1, 0, 0, "avgpool").layernorm(1e-6, True, "head_ln").flatten("flatten")
+            .dense(classes, True, "fc").build())
+
+
+def create_convnext_pico_cifar10() -> Sequential:
+    return _convnext("ConvNeXt-Pico-CIFAR10", 32, 2, (2, 2, 6, 2), (64, 128, 256, 512), 10)
+
+
+def create_convnext_tiny_tiny_imagenet() -> Sequential:
+    return _convnext("ConvNeXt-T-Tiny-ImageNet", 64, 4, (3, 3, 9, 3), (96, 192, 384, 768), 200)
+
+
 MODELS = {
     "mnist_cnn": create_mnist_trainer,
     "cifar10_cnn_v1": create_cifar10_trainer_v1,
@@ -251,6 +275,8 @@ MODELS = {
     "mobilenet_v1_tiny_imagenet": create_mobilenet_v1_tiny_imagenet,
     "resnext50_32x4d_tiny_imagenet": create_resnext50_32x4d_tiny_imagenet,
     "resnext26_32x4d_cifar10": create_resnext26_32x4d_cifar10,
+    "convnext_pico_cifar10": create_convnext_pico_cifar10,
+    "convnext_tiny_tiny_imagenet": create_convnext_tiny_tiny_imagenet,
 }
 
 INPUT_SHAPES = {
@@ -261,6 +287,7 @@ INPUT_SHAPES = {
     "resnet50_tiny_imagenet": (3, 64, 64), "resnet50_imagenet": (3, 224, 224),
     "mobilenet_v1_cifar10": (3, 32, 32), "mobilenet_v1_tiny_imagenet": (3, 64, 64),
     "resnext50_32x4d_tiny_imagenet": (3, 64, 64), "resnext26_32x4d_cifar10": (3, 32, 32),
+    "convnext_pico_cifar10": (3, 32, 32), "convnext_tiny_tiny_imagenet": (3, 64, 64),
 }
 
 NUM_CLASSES = {k: (10 if ("cifar" in k or "mnist" in k) else (1000 if k == "resnet50_imagenet" else 200))

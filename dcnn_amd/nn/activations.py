@@ -1,6 +1,7 @@
 """Activation functions + factory (reference `include/nn/activations.hpp:27-64`,
 `include/nn/activations_impl/*`): relu, leaky_relu(0.01), elu(1.0), sigmoid, tanh,
-softmax (over the channel dim per spatial location), linear; "none" -> None.
+softmax (over the channel dim per spatial location), linear, gelu (exact, x * Phi(x); no
+reference counterpart); "none" -> None.
 
 Each function has a CPU (native C++ backend, csrc/native/cpu_ops.cpp) and a GPU (HIP kernel)
 implementation of ``apply(x)`` and ``gradient(x, y, grad)`` (x = input, y = output); the ATen
@@ -101,6 +102,18 @@ class Tanh(ActivationFunction):
         return g * (1 - t * t)
 
 
+class GELU(ActivationFunction):
+    """Exact GELU x * Phi(x) (erf form); gradient Phi(x) + x * phi(x)."""
+    name_str = "gelu"
+
+    def _cpu(self, x):
+        return torch.nn.functional.gelu(x)
+
+    def _cpu_grad(self, x, y, g):
+        cdf = 0.5 * (1 + torch.erf(x * 0.7071067811865476))
+        return g * (cdf + x * torch.exp(-0.5 * x * x) * 0.3989422804014327)
+
+
 class Linear(ActivationFunction):
     name_str = "linear"
 
@@ -147,6 +160,7 @@ class ActivationFactory:
         cls.register_activation("linear", Linear)
         cls.register_activation("tanh", Tanh)
         cls.register_activation("elu", lambda: ELU(1.0))
+        cls.register_activation("gelu", GELU)
 
     @classmethod
     def create(cls, name: str) -> Optional[ActivationFunction]:

@@ -8,7 +8,7 @@ from typing import Callable, Dict, List, Optional
 from .base import Layer, LayerConfig, ParameterizedLayer, StatelessLayer
 from .conv import Conv2D, Dense, DepthwiseConv2D, GroupedConv2D
 from .misc import Activation, AvgPool2D, Dropout, Flatten, MaxPool2D
-from .norm import BatchNorm, GroupNorm
+from .norm import BatchNorm, GroupNorm, LayerNorm, LayerScale
 from .residual import ResidualBlock, plan_fusion
 
 
@@ -22,7 +22,7 @@ class LayerFactory:
     @classmethod
     def register_defaults(cls) -> None:
         for L in (Dense, Conv2D, DepthwiseConv2D, GroupedConv2D, Activation, MaxPool2D, AvgPool2D, Dropout, BatchNorm,
-                  GroupNorm, Flatten, ResidualBlock):
+                  GroupNorm, LayerNorm, LayerScale, Flatten, ResidualBlock):
             cls.register_layer(L.type_name, L.from_config)
 
     @classmethod
@@ -111,6 +111,14 @@ class LayerBuilder:
         s = self.get_current_shape()
         return self.add_layer(GroupNorm(int(num_groups), s[1], epsilon, affine, self._auto(name, "groupnorm")))
 
+    def layernorm(self, epsilon=1e-6, affine=True, name=""):
+        s = self.get_current_shape()
+        return self.add_layer(LayerNorm(s[1], epsilon, affine, self._auto(name, "layernorm")))
+
+    def layer_scale(self, init_value=1e-6, name=""):
+        s = self.get_current_shape()
+        return self.add_layer(LayerScale(s[1], init_value, self._auto(name, "layer_scale")))
+
     def activation(self, activation_name, name=""):
         return self.add_layer(Activation(activation_name, self._auto(name, "activation")))
 
@@ -138,5 +146,5 @@ def residual_block(main_path, shortcut_path, activation="relu", name="residual_b
 
 
 __all__ = ["Layer", "LayerConfig", "ParameterizedLayer", "StatelessLayer", "Conv2D", "DepthwiseConv2D", "GroupedConv2D", "Dense",
-           "BatchNorm", "GroupNorm", "MaxPool2D", "AvgPool2D", "Dropout", "Flatten", "Activation", "ResidualBlock",
+           "BatchNorm", "GroupNorm", "LayerNorm", "LayerScale", "MaxPool2D", "AvgPool2D", "Dropout", "Flatten", "Activation", "ResidualBlock",
            "LayerFactory", "LayerBuilder", "create_layer", "residual_block", "plan_fusion"]

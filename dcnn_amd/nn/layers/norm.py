@@ -1,4 +1,5 @@
-"""BatchNorm and GroupNorm layers.
+"""BatchNorm, GroupNorm, channel LayerNorm and LayerScale layers (the last two have no reference
+counterpart: lnorm.hip on the GPU, layernorm_* / layer_scale_* of the native CPU backend).
 
 Reference: `include/nn/layers_impl/batchnorm_layer.tpp:27-369`,
 `include/nn/layers_impl/groupnorm_layer.tpp:21-321`. GPU path: split-reduction statistics
@@ -315,3 +316,161 @@ class GroupNorm(ParameterizedLayer):
         p = cfg.parameters
         return GroupNorm(int(p["num_groups"]), p["num_channels"], p.get("epsilon", 1e-5), p.get("affine", True),
                          cfg.name or "groupnorm")
+
+
+class LayerNorm(ParameterizedLayer):
+    """Channel LayerNorm: every (n, h, w) position of a 4-D input is normalised over its C
+    channels (``F.layer_norm`` over the channel dimension; a 2-D ``[N, F]`` input is H = W = 1).
+    ``GroupNorm(1, C)`` normalises over C*H*W and BatchNorm over N*H*W: neither is this. GPU:
+    lnorm.hip (one read and one write forward, two reads and one write backward)."""
+    type_name = "layernorm"
+
+    def __init__(self, num_channels: int, epsilon: float = 1e-6, affine: bool = True, name: str = "layernorm"):
+        super().__init__(name)
+        self.num_channels = int(num_channels)
+        self.epsilon = float(epsilon)
+        self.affine = bool(affine)
+
+    def param_specs(self):
+        if not self.affine:
+            return []
+        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1)), ParamSpec("beta", (self.num_channels, 1, 1, 1))]
+
+    def init_values(self, gen):
+        if not self.affine:
+            return []
+        return [torch.ones((self.num_channels, 1, 1, 1)), torch.zeros((self.num_channels, 1, 1, 1))]
+
+    def has_parameters(self):
+        return self.affine
+
+    def _check(self, x):
+        if x.dim() not in (2, 4) or x.shape[1] != self.num_channels:
+            raise ValueError(f"LayerNorm '{self.name}': expected a [N, {self.num_channels}, H, W] or "
+                             f"[N, {self.num_channels}] input, got {tuple(x.shape)}")
+
+    def _gpu_act(self, t):
+        from ...ops import hip
+        if t.dim() == 4:
+            return hip.to_act(t, self.compute_dtype)
+        return t.to(self.compute_dtype).contiguous()
+
+    def forward(self, x, mb_id=0):
+        x = self._to_layer_device(x)
+        self._check(x)
+        gamma = self._params[0].view(-1) if self.affine else None
+        beta = self._params[1].view(-1) if self.affine else None
+        if x.is_cuda:
+            from ...ops import hip
+            xa = self._gpu_act(x)
+            y, mean, rstd = hip.ln_fwd(xa, gamma, beta, self.epsilon)
+            self._cache[mb_id] = (xa, mean, rstd)
+            return y
+        from ...ops import cpu
+        y, mean, rstd = cpu.layernorm_fwd(x, gamma, beta, self.epsilon)
+        self._cache[mb_id] = (x, mean, rstd)
+        return y
+
+    def backward(self, grad, mb_id=0):
+        ent = self._cache.pop(mb_id, None)
+        if ent is None:
+            raise RuntimeError(f"LayerNorm '{self.name}': no cached data for micro-batch {mb_id}")
+        x, mean, rstd = ent
+        gamma = self._params[0].view(-1) if self.affine else None
+        dg = self._grads[0].view(-1) if self.affine else None
+        db = self._grads[1].view(-1) if self.affine else None
+        if x.is_cuda:
+            from ...ops import hip
+            return hip.ln_bwd(self._gpu_act(grad.to(x.device)), x, gamma, mean, rstd, dg, db)
+        from ...ops import cpu
+        return cpu.layernorm_bwd(x, grad.to(x.dtype), gamma, mean, rstd, dg, db)
+
+    def forward_flops(self, s):
+        n = 1
+        for d in s:
+            n *= d
+        return 6 * n  # statistics (2) + normalise (2) + affine (2)
+
+    def backward_flops(self, s):
+        n = 1
+        for d in s:
+            n *= d
+        return 9 * n
+
+    def get_config(self):
+        return LayerConfig(self.name, dict(num_channels=self.num_channels, epsilon=self.epsilon, affine=self.affine),
+                           self.type_name)
+
+    @staticmethod
+    def from_config(cfg):
+        p = cfg.parameters
+        return LayerNorm(p["num_channels"], p.get("epsilon", 1e-6), p.get("affine", True), cfg.name or "layernorm")
+
+
+class LayerScale(ParameterizedLayer):
+    """Learnable per-channel scale ``y = gamma[c] * x`` (the layer scale of a ConvNeXt / CaiT
+    residual branch). ``forward(x, mb_id, residual=r)`` returns ``r + gamma * x`` from the same
+    store (a residual block's scale tail, RF_SCALE_TAIL in the shared planner)."""
+    type_name = "layer_scale"
+
+    def __init__(self, num_channels: int, init_value: float = 1e-6, name: str = "layer_scale"):
+        super().__init__(name)
+        self.num_channels = int(num_channels)
+        self.init_value = float(init_value)
+
+    def param_specs(self):
+        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1))]
+
+    def init_values(self, gen):
+        return [torch.full((self.num_channels, 1, 1, 1), self.init_value)]
+
+    def _check(self, x):
+        if x.dim() not in (2, 4) or x.shape[1] != self.num_channels:
+            raise ValueError(f"LayerScale '{self.name}': expected a [N, {self.num_channels}, H, W] or "
+                             f"[N, {self.num_channels}] input, got {tuple(x.shape)}")
+
+    _gpu_act = LayerNorm._gpu_act
+
+    def forward(self, x, mb_id=0, residual=None):
+        x = self._to_layer_device(x)
+        self._check(x)
+        gamma = self._params[0].view(-1)
+        if x.is_cuda:
+            from ...ops import hip
+            xa = self._gpu_act(x)
+            self._cache[mb_id] = xa
+            return hip.lscale_fwd(xa, gamma, None if residual is None else self._gpu_act(residual))
+        from ...ops import cpu
+        self._cache[mb_id] = x
+        return cpu.layer_scale_fwd(x, gamma, None if residual is None else residual.to(x.dtype))
+
+    def backward(self, grad, mb_id=0):
+        x = self._cache.pop(mb_id, None)
+        if x is None:
+            raise RuntimeError(f"LayerScale '{self.name}': no cached data for micro-batch {mb_id}")
+        gamma, dg = self._params[0].view(-1), self._grads[0].view(-1)
+        if x.is_cuda:
+            from ...ops import hip
+            return hip.lscale_bwd(self._gpu_act(grad.to(x.device)), x, gamma, dg)
+        from ...ops import cpu
+        return cpu.layer_scale_bwd(x, grad.to(x.dtype), gamma, dg, need_dx=self.needs_input_grad)
+
+    def forward_flops(self, s):
+        n = 1
+        for d in s:
+            n *= d
+        return n
+
+    def backward_flops(self, s):
+        n = 1
+        for d in s:
+            n *= d
+        return 3 * n
+
+    def get_config(self):
+        return LayerConfig(self.name, dict(num_channels=self.num_channels, init_value=self.init_value), self.type_name)
+
+    @staticmethod
+    def from_config(cfg):
+        p = cfg.parameters
+        return LayerScale(p["num_channels"], p.get("init_value", 1e-6), cfg.name or "layer_scale")

@@ -3,7 +3,9 @@
 GPU path fuses the tail of the block: the last BatchNorm of F applies ``+ S(x)`` and the ReLU
 in the same pass (no pre-activation tensor, no separate add/ReLU kernels), its backward emits
 the ReLU-masked gradient once for both branches, and the branch sum ``dF + dS`` is fused into
-the epilogue of the first conv's dgrad GEMM.
+the epilogue of the first conv's dgrad GEMM. A block whose main path closes in a LayerScale, with
+an identity shortcut and no activation (ConvNeXt), takes the scale tail: the LayerScale's store
+writes ``x + gamma * F(x)`` and the first layer's data gradient adds the shortcut gradient.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ from ..activations import ActivationFactory
 from .base import LayerConfig, Layer, run_backward
 from .conv import Conv2D, DepthwiseConv2D, GroupedConv2D
 from .misc import Activation, MaxPool2D
-from .norm import BatchNorm
+from .norm import BatchNorm, LayerScale
 
 
 def fuse_kinds(layers: List[Layer]) -> List[int]:
@@ -33,6 +35,8 @@ def fuse_kinds(layers: List[Layer]) -> List[int]:
             out.append(K.FK_RELU if l.activation_name == "relu" else K.FK_ACT)
         elif isinstance(l, MaxPool2D):
             out.append(K.FK_MAXPOOL)
+        elif isinstance(l, LayerScale):
+            out.append(K.FK_LSCALE)
         else:
             out.append(K.FK_OTHER)
     return out
@@ -80,7 +84,7 @@ class ResidualBlock(Layer):
         self.shortcut_path = list(shortcut_path or [])
         self.activation_type = activation
         self.act = ActivationFactory.create(activation)
-        self._fused = self._dual = False
+        self._fused = self._dual = self._scale_tail = False
 
     # structure -------------------------------------------------------------------------
     def sublayers(self) -> List[Layer]:
@@ -133,13 +137,15 @@ class ResidualBlock(Layer):
         plan_fusion(self.main_path, on_gpu)
         plan_fusion(self.shortcut_path, on_gpu)
         act_ok = self.activation_type in ("relu", "none", "linear")
-        self._fused = self._dual = False
+        self._fused = self._dual = self._scale_tail = False
         if on_gpu:  # the shared planner's residual rules (fusion_plan.cpp, plan_residual_fusions)
             from ...ops._ext import kernels
             K = kernels()
-            rf = K.plan_residual_fusions(fuse_kinds(self.main_path), fuse_kinds(self.shortcut_path), act_ok)
+            rf = K.plan_residual_fusions(fuse_kinds(self.main_path), fuse_kinds(self.shortcut_path), act_ok,
+                                         self.activation_type in ("none", "linear"))
             self._fused = bool(rf & K.RF_FUSED_TAIL)
             self._dual = bool(rf & K.RF_DUAL_SHORTCUT)
+            self._scale_tail = bool(rf & K.RF_SCALE_TAIL)
         if self._fused:
             self.main_path[-1].emit_masked_grad = True
         for l in self.sublayers():
@@ -175,6 +181,15 @@ class ResidualBlock(Layer):
             out = self.main_path[-1].forward(h, mb_id, residual=s if defer else hip.to_act(s, self.compute_dtype),
                                              relu=self.activation_type == "relu")
             self._cache[mb_id] = ("fused", None)
+            return out
+        if self._scale_tail:
+            from ...ops import hip
+            xa = hip.to_act(x, self.compute_dtype)
+            h = xa
+            for l in self.main_path[:-1]:
+                h = l.forward(h, mb_id)
+            out = self.main_path[-1].forward(h, mb_id, residual=xa)  # x + gamma * F(x) in one store
+            self._cache[mb_id] = ("scale", None)
             return out
         h = x
         for l in self.main_path:
@@ -218,6 +233,18 @@ class ResidualBlock(Layer):
             if isinstance(first, (DepthwiseConv2D, GroupedConv2D)):
                 return first.backward(g, mb_id, add_to=d_s)  # dF + dS in the dgrad's store
             return first.backward(g, mb_id) + d_s
+        if kind == "scale":
+            # the shortcut gradient is `grad` itself: the first layer's data gradient adds it
+            g = grad
+            for k in range(len(self.main_path) - 1, 0, -1):
+                g = run_backward(self.main_path, k, g, mb_id)
+            first = self.main_path[0]
+            if not self.needs_input_grad:
+                first.backward(g, mb_id)
+                return None
+            if isinstance(first, (Conv2D, DepthwiseConv2D, GroupedConv2D)):
+                return first.backward(g, mb_id, add_to=grad)
+            return first.backward(g, mb_id) + grad
         pre, out = ent
         g = self.act.gradient(pre, out, grad) if self.act is not None else grad
         d_main = g

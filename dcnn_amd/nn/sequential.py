@@ -29,8 +29,8 @@ import torch
 
 from ..device import Device, DeviceType, get_cpu, get_device
 from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten, GroupNorm,
-                     GroupedConv2D, Layer, LayerBuilder, LayerConfig, LayerFactory, MaxPool2D, ParameterizedLayer,
-                     ResidualBlock, create_layer, plan_fusion)
+                     GroupedConv2D, Layer, LayerBuilder, LayerConfig, LayerFactory, LayerNorm, LayerScale, MaxPool2D,
+                     ParameterizedLayer, ResidualBlock, create_layer, plan_fusion)
 from .layers.base import run_backward
 from .params import ParamArena
 
@@ -767,6 +767,31 @@ class SequentialBuilder:
             short = (LayerBuilder().input(shape).conv2d(out_channels, 1, 1, stride, stride, 0, 0, False)
                      .batchnorm(1e-3, 0.1, True, "bn0").build())
         return self._add(ResidualBlock(main, short, "relu", name))
+
+    def layernorm(self, epsilon=1e-6, affine=True, name=""):
+        return self._add(LayerNorm(self._shape[1], epsilon, affine, self._n(name, "layernorm")))
+
+    def layer_scale(self, init_value=1e-6, name=""):
+        return self._add(LayerScale(self._shape[1], init_value, self._n(name, "layer_scale")))
+
+    def convnext_block(self, channels, layer_scale_init=1e-6, name="convnext_block"):
+        """ConvNeXt block (Liu et al. 2022): x + LayerScale(1x1(GELU(1x1(LayerNorm(dw7x7(x)))))), an
+        identity-shortcut residual block without activation (the scale tail on the GPU)."""
+        shape = [channels, self._shape[2], self._shape[3]]
+        main = (LayerBuilder().input(shape)
+                .depthwise_conv2d(7, 7, 1, 1, 3, 3, True)
+                .layernorm(1e-6, True)
+                .conv2d(4 * channels, 1, 1, 1, 1, 0, 0, True)
+                .activation("gelu")
+                .conv2d(channels, 1, 1, 1, 1, 0, 0, True)
+                .layer_scale(layer_scale_init)
+                .build())
+        return self._add(ResidualBlock(main, [], "none", name))
+
+    def convnext_downsample(self, out_channels, name="convnext_downsample"):
+        """ConvNeXt stage transition: LayerNorm, then a 2x2 / stride-2 conv (``name``_ln, ``name``_conv)."""
+        self.layernorm(1e-6, True, f"{name}_ln")
+        return self.conv2d(out_channels, 2, 2, 2, 2, 0, 0, True, f"{name}_conv")
 
     def build(self) -> Sequential:
         if not hasattr(self, "_shape"):

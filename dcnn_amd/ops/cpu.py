@@ -17,7 +17,7 @@ import torch
 from ._ext import native
 
 _DT = {torch.float32: 0, torch.float64: 1}
-ACT_CODES = {"linear": 0, "relu": 1, "leaky_relu": 2, "elu": 3, "sigmoid": 4, "tanh": 5}
+ACT_CODES = {"linear": 0, "relu": 1, "leaky_relu": 2, "elu": 3, "sigmoid": 4, "tanh": 5, "gelu": 6}
 LOSS_CODES = {"crossentropy": 0, "softmax_crossentropy": 1, "logsoftmax_crossentropy": 1, "mse": 2, "mae": 3,
               "huber": 4}
 
@@ -347,6 +347,61 @@ def groupnorm_bwd(x, dy, G, gamma, mean, istd, dgamma, dbeta):
     dx = torch.empty_like(x)
     C().groupnorm_bwd(dt(x), x.data_ptr(), dy.data_ptr(), mean.data_ptr(), istd.data_ptr(), p(gamma), dx.data_ptr(),
                       p(dgamma), p(dbeta), N, Cc, H * W, G)
+    return dx
+
+
+def _nchw_rows(x):
+    """(N, C, HW) of a [N, C, ...] tensor (a 2-D [N, F] input: HW = 1)."""
+    if x.dim() < 2:
+        raise ValueError(f"expected a [N, C, ...] tensor, got {tuple(x.shape)}")
+    N, Cc = x.shape[0], x.shape[1]
+    return N, Cc, x.numel() // max(N * Cc, 1)
+
+
+def layernorm_fwd(x, gamma, beta, eps):
+    """Channel LayerNorm: every (n, position) of x [N, C, ...] over its C channels. Returns
+    (y, mean, rstd), the statistics as [N * HW]."""
+    x = _c(x)
+    _same(x, gamma, beta)
+    N, Cc, HW = _nchw_rows(x)
+    y = torch.empty_like(x)
+    mean = torch.empty(N * HW, dtype=x.dtype)
+    rstd = torch.empty(N * HW, dtype=x.dtype)
+    C().layernorm_fwd(dt(x), x.data_ptr(), y.data_ptr(), N, Cc, HW, p(gamma), p(beta), float(eps), mean.data_ptr(),
+                      rstd.data_ptr())
+    return y, mean, rstd
+
+
+def layernorm_bwd(x, dy, gamma, mean, rstd, dgamma, dbeta):
+    """dgamma += sum dy xhat, dbeta += sum dy; returns dx."""
+    x, dy = _c(x), _c(dy)
+    _same(x, dy, gamma, mean, rstd, dgamma, dbeta)
+    N, Cc, HW = _nchw_rows(x)
+    dx = torch.empty_like(x)
+    C().layernorm_bwd(dt(x), x.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(), p(gamma), dx.data_ptr(),
+                      p(dgamma), p(dbeta), N, Cc, HW)
+    return dx
+
+
+def layer_scale_fwd(x, gamma, residual=None):
+    """y = gamma[c] * x (+ residual)."""
+    x, residual = _c(x), _c(residual)
+    _same(x, gamma, residual)
+    N, Cc, HW = _nchw_rows(x)
+    if gamma.numel() != Cc or (residual is not None and residual.shape != x.shape):
+        raise ValueError(f"layer_scale: x {tuple(x.shape)}, gamma {gamma.numel()} values")
+    y = torch.empty_like(x)
+    C().layer_scale_fwd(dt(x), x.data_ptr(), gamma.data_ptr(), p(residual), y.data_ptr(), N, Cc, HW)
+    return y
+
+
+def layer_scale_bwd(x, dy, gamma, dgamma, need_dx=True):
+    """dgamma += sum dy x; returns dx = gamma[c] * dy (or None)."""
+    x, dy = _c(x), _c(dy)
+    _same(x, dy, gamma, dgamma)
+    N, Cc, HW = _nchw_rows(x)
+    dx = torch.empty_like(x) if need_dx else None
+    C().layer_scale_bwd(dt(x), x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), p(dx), p(dgamma), N, Cc, HW)
     return dx
 
 

@@ -7,7 +7,8 @@ from ..runtime import arena as _arena
 from . import fusion
 from ._ext import dt_code, kernels, ptr, stream_ptr
 from .hip_base import (BF16, CL, F32, PLAIN, _check_act, _empty, _empty_like, _g2_ok, _nbytes,
-                       _reduce_wb, _ticket, conv_out_hw, pool_out_hw)
+                       _rec, _reduce_wb, _ticket, conv_out_hw, pool_out_hw)
+from .hip_norm import _ln_like, ln_rows
 
 
 def dense_fwd(x2d, w2d, bias):
@@ -131,7 +132,7 @@ def avgpool_bwd(dy, x_shape, ph, pw, sh, sw, pdh, pdw):
 
 
 # ------------------------------------------------------------------------------ activations
-ACT_CODES = {"relu": 0, "leaky_relu": 1, "elu": 2, "sigmoid": 3, "tanh": 4, "linear": 5}
+ACT_CODES = {"relu": 0, "leaky_relu": 1, "elu": 2, "sigmoid": 3, "tanh": 4, "linear": 5, "gelu": 6}
 
 
 def act_fwd(x, kind, alpha=0.01):
@@ -146,6 +147,36 @@ def act_bwd(x, dy, kind, alpha=0.01):
     dx = _empty_like(x)
     kernels().act_bwd(dt_code(x.dtype), x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), ACT_CODES[kind],
                       float(alpha), stream_ptr())
+    return dx
+
+
+def lscale_fwd(x, gamma, residual=None):
+    """LayerScale (lnorm.hip): y = gamma[c] * x (+ residual, a same-shape activation, added in
+    the same store); gamma fp32 [C]. x: 4-D channels_last or contiguous 2-D [R, C]."""
+    R, C = ln_rows(x, "lscale_fwd")
+    assert gamma.dtype == F32 and gamma.numel() == C and gamma.is_contiguous(), "lscale_fwd: gamma fp32 [C]"
+    if residual is not None:
+        _ln_like(residual, x, "lscale_fwd.residual")
+    _rec("lscale_fwd", x=tuple(x.shape), residual=residual is not None)
+    y = _empty_like(x)
+    kernels().lscale_fwd(dt_code(x.dtype), x.data_ptr(), gamma.data_ptr(), ptr(residual), y.data_ptr(), R, C,
+                         stream_ptr())
+    return y
+
+
+def lscale_bwd(dy, x, gamma, dgamma):
+    """dx = gamma[c] * dy; dgamma += sum dy * x (fp32 [C]), summed in a fixed order through a
+    per-workgroup slab (bit-reproducible)."""
+    R, C = ln_rows(x, "lscale_bwd")
+    _ln_like(dy, x, "lscale_bwd.dy")
+    for t in (gamma, dgamma):
+        assert t.dtype == F32 and t.numel() == C and t.is_contiguous(), "lscale_bwd: gamma / dgamma fp32 [C]"
+    _rec("lscale_bwd", x=tuple(x.shape))
+    K = kernels()
+    dx = _empty_like(x)
+    ws = _empty((K.ln_partial_rows(R, C), C), F32, x.device)
+    K.lscale_bwd(dt_code(x.dtype), dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), R, C,
+                 ws.data_ptr(), stream_ptr())
     return dx
 
 

@@ -10,7 +10,7 @@ import torch
 from ..runtime import arena as _arena
 from . import fusion
 from ._ext import dt_code, kernels, ptr, stream_ptr
-from .hip_base import BF16, CL, F32, _empty, _empty_like, _rc, _ticket, pool_out_hw
+from .hip_base import BF16, CL, F32, _empty, _empty_like, _rc, _rec, _ticket, pool_out_hw
 
 
 class Stats:
@@ -313,6 +313,73 @@ def bn_backward(dy, x, yout, mean, istd, gamma, dgamma, dbeta, *, want_masked=Fa
                    mean.data_ptr(), istd.data_ptr(), ptr(gamma), sp, parts, float(R), ptr(dgamma), ptr(dbeta),
                    int(eval_mode), st)
     return dx, dmask
+
+
+def ln_rows(x, what):
+    """(R, C) of a channel-LayerNorm / LayerScale operand: a 4-D channels_last activation is
+    R = N H W rows of C channels, a contiguous 2-D [R, C] tensor is itself. A shape or dtype the
+    kernels (lnorm.hip) do not take is an error naming it (never a fallback)."""
+    if not x.is_cuda:
+        raise ValueError(f"{what}: expected a GPU tensor")
+    if x.dim() == 4 and x.is_contiguous(memory_format=CL):
+        R, C = x.shape[0] * x.shape[2] * x.shape[3], x.shape[1]
+    elif x.dim() == 2 and x.is_contiguous():
+        R, C = x.shape
+    else:
+        raise ValueError(f"{what}: expected a channels_last 4-D or contiguous 2-D tensor, got {tuple(x.shape)} "
+                         f"strides {tuple(x.stride())}")
+    if x.dtype not in (F32, BF16) or not kernels().ln_supported(dt_code(x.dtype), R, C):
+        raise ValueError(f"{what}: unsupported shape: x {tuple(x.shape)} {x.dtype} = {R} rows of C={C} channels "
+                         f"(needs C % {4 if x.dtype == F32 else 8} == 0, 8 <= C <= 2048, fewer than 2^31 elements)")
+    return R, C
+
+
+def _ln_param(t, C, what):
+    if t is not None:
+        assert t.dtype == F32 and t.numel() == C and t.is_contiguous(), f"{what}: fp32 [C] expected"
+    return t
+
+
+def _ln_like(t, x, what):
+    """t is a second operand of x's shape, dtype and row layout"""
+    ok = t.is_contiguous(memory_format=CL) if x.dim() == 4 else t.is_contiguous()
+    if tuple(t.shape) != tuple(x.shape) or t.dtype != x.dtype or not t.is_cuda or not ok:
+        raise ValueError(f"{what}: {tuple(t.shape)} {t.dtype} does not match x {tuple(x.shape)} {x.dtype} "
+                         f"(same shape, dtype and memory layout expected)")
+
+
+def ln_fwd(x, gamma, beta, eps):
+    """Channel LayerNorm (lnorm.hip): y = (x - mean) * rstd * gamma + beta over the C channels of
+    every row; gamma / beta fp32 [C] or None. Returns (y, mean, rstd), the statistics fp32 [R]."""
+    R, C = ln_rows(x, "ln_fwd")
+    _ln_param(gamma, C, "ln_fwd.gamma")
+    _ln_param(beta, C, "ln_fwd.beta")
+    _rec("ln_fwd", x=tuple(x.shape), affine=gamma is not None)
+    y = _empty_like(x)
+    mean = _empty((R,), F32, x.device)
+    rstd = _empty((R,), F32, x.device)
+    kernels().ln_fwd(dt_code(x.dtype), x.data_ptr(), y.data_ptr(), R, C, ptr(gamma), ptr(beta), float(eps),
+                     mean.data_ptr(), rstd.data_ptr(), stream_ptr())
+    return y, mean, rstd
+
+
+def ln_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta):
+    """dx of :func:`ln_fwd`; dgamma += sum dy * xhat, dbeta += sum dy (fp32 [C] or None), summed
+    in a fixed order through a per-workgroup slab (bit-reproducible)."""
+    R, C = ln_rows(x, "ln_bwd")
+    _ln_like(dy, x, "ln_bwd.dy")
+    _ln_param(gamma, C, "ln_bwd.gamma")
+    _ln_param(dgamma, C, "ln_bwd.dgamma")
+    _ln_param(dbeta, C, "ln_bwd.dbeta")
+    _rec("ln_bwd", x=tuple(x.shape), affine=dgamma is not None)
+    K = kernels()
+    dx = _empty_like(x)
+    ws = None
+    if dgamma is not None or dbeta is not None:
+        ws = _empty((K.ln_partial_rows(R, C), 2, C), F32, x.device)
+    K.ln_bwd(dt_code(x.dtype), dy.data_ptr(), x.data_ptr(), dx.data_ptr(), R, C, ptr(gamma), mean.data_ptr(),
+             rstd.data_ptr(), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+    return dx
 
 
 def gn_fwd(x, groups, gamma, beta, eps):
