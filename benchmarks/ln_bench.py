@@ -15,6 +15,12 @@ These tensors (0.8 - 19 MB) fit the last-level cache: the rates are cache rates,
 copy, which is why the copy and not an HBM peak is the yardstick.
 
   python benchmarks/ln_bench.py [--batch 128] [--md ln_bench.md]
+
+``--drop-path`` measures stochastic depth instead (profiles/drop_path.md): at the ConvNeXt-pico and
+ConvNeXt-T block shapes, the fused drop tail (lscale_drop_fwd / lscale_drop_bwd, mask drawn at
+``--rate``) against the unmasked scale tail (lscale_fwd with residual / lscale_bwd) and against the
+unfused composition (LayerScale, standalone DropPath, add), the three alternating round after round;
+then a ConvNeXt-pico training step (captured) at drop-path rates 0 and ``--rate``, alternating.
 """
 import argparse
 import json
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--replays", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--md", default=None, help="also write the markdown table to this file")
+    ap.add_argument("--drop-path", action="store_true", help="the stochastic-depth rows instead")
+    ap.add_argument("--rate", type=float, default=0.1, help="--drop-path: the drop rate of the mask")
+    ap.add_argument("--steps", type=int, default=30, help="--drop-path: training steps per window")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ln_bench: needs a GPU (nothing is measured without one)")
@@ -69,6 +78,9 @@ def main():
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) * 1e3 / (a.replays * a.iters)  # us per call
         return run
+
+    if a.drop_path:
+        return drop_path_rows(a, window)
 
     rows = []
     lines = ["| shape R x C | op | tensors | MB | ours us | ours TB/s | copy us | % of copy | torch us | torch / ours |",
@@ -118,6 +130,91 @@ def main():
             lines.append(f"| {R} x {t.shape[1]} | {op} | {nt} | {mb:.2f} | {us:.2f} | {mb / us:.2f} | {cp:.2f} | "
                          f"{100 * cp / us:.0f}% | {th:.2f} | {th / us:.2f} |")
             print(lines[-1], flush=True)
+    for r in rows:
+        print(json.dumps(r))
+    if a.md:
+        with open(a.md, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def drop_path_rows(a, window):
+    from dcnn_amd.ops import hip
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    N = a.batch
+    # (model, C, map side): ConvNeXt-pico on 32x32 inputs, ConvNeXt-T on 64x64
+    shapes = [("pico", 64, 16), ("pico", 128, 8), ("pico", 256, 4), ("pico", 512, 2),
+              ("T", 96, 16), ("T", 192, 8), ("T", 384, 4), ("T", 768, 2)]
+    lines = ["| model | N x C x H x W | pass | drop tail us | scale tail us | unfused us | drop / scale | drop / unfused "
+             "| spread drop us | spread scale us |", "|---|---|---|---:|---:|---:|---:|---:|---|---|"]
+    print("\n".join(lines), flush=True)
+    rows = []
+    for model, C, side in shapes:
+        mk = lambda: torch.randn(N, C, side, side, generator=g).to(dev).to(torch.bfloat16).contiguous(  # noqa: E731
+            memory_format=torch.channels_last)
+        x, dy, res = mk(), mk(), mk()
+        gamma = (1 + 0.1 * torch.randn(C, generator=g)).to(dev)
+        dg = torch.zeros(C, device=dev)
+        mask = hip.drop_path_mask(torch.zeros(N, device=dev), a.rate, 1234, draw=1)
+        passes = [
+            ("fwd", lambda: hip.lscale_drop_fwd(x, gamma, mask, res), lambda: hip.lscale_fwd(x, gamma, res),
+             lambda: hip.drop_path_scale(hip.lscale_fwd(x, gamma), mask) + res),
+            ("bwd", lambda: hip.lscale_drop_bwd(dy, x, gamma, mask, dg), lambda: hip.lscale_bwd(dy, x, gamma, dg),
+             lambda: hip.lscale_bwd(hip.drop_path_scale(dy, mask), x, gamma, dg)),
+        ]
+        for nm, fused, plain, unfused in passes:
+            wins = [window(fused), window(plain), window(unfused)]
+            ts = [[], [], []]
+            for _ in range(a.rounds):  # alternate the three
+                for k, w in enumerate(wins):
+                    ts[k].append(w())
+            f, p, u = (statistics.median(v) for v in ts)
+            r = dict(model=model, shape=[N, C, side, side], op=nm, rate=a.rate, kept=int((mask != 0).sum()),
+                     drop_tail_us=round(f, 2), scale_tail_us=round(p, 2), unfused_us=round(u, 2),
+                     spread_drop_us=[round(min(ts[0]), 2), round(max(ts[0]), 2)],
+                     spread_scale_us=[round(min(ts[1]), 2), round(max(ts[1]), 2)],
+                     spread_unfused_us=[round(min(ts[2]), 2), round(max(ts[2]), 2)])
+            rows.append(r)
+            lines.append(f"| {model} | {N} x {C} x {side} x {side} | {nm} | {f:.2f} | {p:.2f} | {u:.2f} | {f / p:.2f} | "
+                         f"{f / u:.2f} | {min(ts[0]):.2f} - {max(ts[0]):.2f} | {min(ts[1]):.2f} - {max(ts[1]):.2f} |")
+            print(lines[-1], flush=True)
+    # a ConvNeXt-pico training step (captured whole) at rates 0 and --rate, alternating windows
+    from dcnn_amd.models import create_model
+    from dcnn_amd.nn import AdamW, LossFactory
+    from dcnn_amd.runtime.step import TrainStep
+    xb = torch.randn(N, 3, 32, 32, generator=g).to(dev)
+    yb = torch.randint(0, 10, (N,), generator=g).to(dev)
+    steps = {}
+    for rate in (0.0, a.rate):
+        m = create_model("convnext_pico_cifar10", drop_path_rate=rate)
+        m.set_seed(1)
+        m.set_device("GPU:0")
+        m.initialize()
+        m.set_first_layer_input_grad(False)
+        opt = AdamW(1e-3, weight_decay=0.05)
+        opt.attach(m)
+        st = TrainStep(m, LossFactory.create("softmax_crossentropy"), opt, use_graph=True)
+        for _ in range(3):
+            st(xb, yb)
+        torch.cuda.synchronize()
+        steps[rate] = st
+    ts = {r: [] for r in steps}
+    for _ in range(a.rounds):
+        for rate, st in steps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                st(xb, yb)
+            e1.record()
+            torch.cuda.synchronize()
+            ts[rate].append(e0.elapsed_time(e1) / a.steps)  # ms per step
+    lines += ["", "| ConvNeXt-pico step, batch | drop-path rate | ms / step (median) | spread ms | img/s |", "|---|---:|---:|---|---:|"]
+    for rate, v in ts.items():
+        med = statistics.median(v)
+        rows.append(dict(model="pico step", batch=N, rate=rate, ms_per_step=round(med, 3),
+                         spread_ms=[round(min(v), 3), round(max(v), 3)], img_per_s=round(N / med * 1e3, 1)))
+        lines.append(f"| {N} | {rate} | {med:.3f} | {min(v):.3f} - {max(v):.3f} | {N / med * 1e3:.0f} |")
+        print(lines[-1], flush=True)
     for r in rows:
         print(json.dumps(r))
     if a.md:

@@ -229,4 +229,37 @@ int dcnn_c_layer_scale_bwd(const void* dy, const void* x, const float* gamma, vo
   return guarded([&] { gpu_ops::layer_scale_bwd(dy, x, gamma, dx, dgamma, R, C); });
 }
 
+// Stochastic depth. The mask of (seed, draw): N floats, 0 or 1 / (1 - p), into the device buffer
+// `mask` — the function the kernel module's and the native CPU module's drop_path_mask return.
+int dcnn_c_drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw) {
+  return guarded([&] { gpu_ops::drop_path_mask(mask, N, p, seed, draw); });
+}
+
+// the same on the CPU backend, into a host buffer
+int dcnn_c_drop_path_mask_host(float* mask, long N, float p, uint64_t seed, uint64_t draw) {
+  try {
+    cpu_ops::drop_path_mask(mask, N, p, seed, draw);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+// y[n][:] = mask[n] x[n][:] (+ residual[n][:]), bf16, samples of `row` elements
+int dcnn_c_drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row) {
+  return guarded([&] { gpu_ops::drop_path_scale(x, mask, residual, y, N, row); });
+}
+
+// the drop tail: y = residual + mask[n] gamma[c] x; dx = mask[n] gamma[c] dy, dgamma (+=) sum mask[n] dy x
+int dcnn_c_layer_scale_drop_fwd(const void* x, const float* gamma, const float* mask, const void* residual, void* y,
+                                long R, int C, long rows_per_sample) {
+  return guarded([&] { gpu_ops::layer_scale_drop_fwd(x, gamma, mask, residual, y, R, C, rows_per_sample); });
+}
+
+int dcnn_c_layer_scale_drop_bwd(const void* dy, const void* x, const float* gamma, const float* mask, void* dx,
+                                float* dgamma, long R, int C, long rows_per_sample) {
+  return guarded([&] { gpu_ops::layer_scale_drop_bwd(dy, x, gamma, mask, dx, dgamma, R, C, rows_per_sample); });
+}
+
 }  // extern "C"

@@ -41,6 +41,9 @@ struct Param {
   Layout layout = Layout::NCHW;
   Tensor value, grad, shadow;
   Tensor m, v;  // optimizer state (lazily created)
+  // excluded from weight decay when the optimizer's no_decay_norm_bias is on: set by the owning
+  // layer for biases, norm affines and layer scales (by kind, never by shape)
+  bool no_decay = false;
   std::shared_ptr<ParamArena> arena;  // GPU: the flat buffers value / grad / m / v / shadow live in
 };
 
@@ -50,6 +53,9 @@ struct Param {
 struct ParamArena {
   Tensor value, grad, m, v, shadow;
   size_t n = 0, count = 0;
+  // one byte per 64-element block, 1 where the block belongs to a Param with no_decay (built once
+  // by Sequential::pack_params: static, so a captured optimizer step replays it as it is)
+  Tensor nodecay;
   // every eligible conv's dgrad operand ([C][KH][KW][Co] bf16), regenerated from the shadows in
   // one batched launch after each fused optimizer step (rows: src, dst, Co, T, C)
   Tensor wt_table;
@@ -400,12 +406,49 @@ class LayerScale : public Layer {
   std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override { return in; }
   void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
   Tensor forward(const Tensor& x, bool training) override { return forward_residual(x, nullptr, training); }
-  Tensor forward_residual(const Tensor& x, const Tensor* residual, bool training);  // gamma x + residual
+  // gamma x + residual; with `mask` (fp32 [N], a DropPath's: GPU only) mask[n] gamma x + residual,
+  // and the backward applies the same mask
+  Tensor forward_residual(const Tensor& x, const Tensor* residual, bool training, const Tensor* mask = nullptr);
   Tensor backward(const Tensor& dy) override;
 
  private:
   int c_;
   float init_;
+};
+
+// Stochastic depth: in training every sample n is scaled by m[n], 0 with probability `rate` and
+// 1 / (1 - rate) otherwise, forward and backward; identity in eval or at rate 0. m is one function
+// of (seed, draw, n) (cpu_ops / gpu_ops drop_path_mask, the Python front end's DropPath draws the
+// same floats): draw counts this layer's training forwards from 1; the seed is the explicit one
+// when given (then part of the JSON config), else the one build() derives. GPU: the mask lives in
+// a per-micro-batch device buffer written once per forward, and the draw index in a device word
+// bumped in-stream, so a replayed TrainGraph draws a new mask each time. Closing a residual block
+// behind a LayerScale, the LayerScale's store applies the mask (ResidualBlock::drop_tail).
+class DropPath : public Layer {
+ public:
+  explicit DropPath(float rate, std::string name = "drop_path", bool has_seed = false, uint64_t seed = 0);
+  std::string type() const override { return "drop_path"; }
+  json::Value parameters_config() const override;
+  std::vector<int64_t> output_shape(const std::vector<int64_t>& in) const override { return in; }
+  double flops(const std::vector<int64_t>& in) const override;
+  void build(const std::vector<int64_t>& in, Device dev, uint64_t seed) override;
+  Tensor forward(const Tensor& x, bool training) override;
+  Tensor backward(const Tensor& dy) override;
+  float rate() const { return p_; }
+  uint64_t mask_seed() const { return has_seed_ ? explicit_seed_ : seed_; }
+  // draw the next mask for N samples into the current micro-batch's buffer; nullptr when the layer
+  // is the identity (eval, rate 0). forward and a block's drop tail call it.
+  const Tensor* draw_mask(int64_t N, bool training);
+  // the last mask of the current micro-batch (fp32 [N], on the layer's device)
+  const Tensor& last_mask() { return mbc().a; }
+  // GPU: the device draw counter (a step runner that rolls warm-up steps back rolls it back too)
+  Tensor& draw_counter() { return ctr_; }
+
+ private:
+  float p_;
+  bool has_seed_;
+  uint64_t explicit_seed_, seed_ = 0, draws_ = 0;
+  Tensor ctr_;
 };
 
 // inverted dropout (scale 1 / (1 - p)), identity in eval; the mask is a counter-based function
@@ -498,6 +541,9 @@ class ResidualBlock : public Layer {
   // GPU: the main path's closing LayerScale of an identity-shortcut block without activation: its
   // store adds the block input, the first layer's data gradient adds the shortcut gradient
   class LayerScale* scale_tail() const;
+  // GPU: the DropPath behind that LayerScale (main path closing in LayerScale, DropPath:
+  // RF_DROP_TAIL), whose mask the LayerScale's store applies; null without one
+  class DropPath* drop_tail() const;
 
  private:
   std::vector<std::unique_ptr<Layer>> main_, short_;
@@ -597,10 +643,13 @@ class SequentialBuilder {
   SequentialBuilder& dense(int out_features, bool bias = true, const std::string& name = "");
   SequentialBuilder& groupnorm(int num_groups, float eps = 1e-5f, bool affine = true, const std::string& name = "");
   SequentialBuilder& dropout(float rate, const std::string& name = "");
+  SequentialBuilder& drop_path(float rate, const std::string& name = "");
   SequentialBuilder& layernorm(float eps = 1e-6f, bool affine = true, const std::string& name = "");
   SequentialBuilder& layer_scale(float init_value = 1e-6f, const std::string& name = "");
   // ConvNeXt block: dw7x7 - LayerNorm - 1x1 (4x) - GELU - 1x1 - LayerScale, identity shortcut, no activation
-  SequentialBuilder& convnext_block(int channels, float layer_scale_init = 1e-6f, const std::string& name = "");
+  // [- DropPath when drop_path > 0, with an explicit seed when has_seed]
+  SequentialBuilder& convnext_block(int channels, float layer_scale_init = 1e-6f, const std::string& name = "",
+                                    float drop_path = 0.f, bool has_seed = false, uint64_t drop_path_seed = 0);
   // ConvNeXt stage transition: LayerNorm (name_ln), then a 2x2 / stride-2 conv (name_conv)
   SequentialBuilder& convnext_downsample(int out_ch, const std::string& name = "convnext_downsample");
   // generic residual block from prebuilt paths (shapes must agree)
@@ -663,6 +712,10 @@ class Adam : public Optimizer {
                 bool decoupled = false)
       : Optimizer(lr), b1_(b1), b2_(b2), eps_(eps), wd_(wd), decoupled_(decoupled) {}
   void step(const std::vector<Param*>& params) override;
+  // biases, norm affines and layer scales (Param::no_decay) take the step without weight decay; on
+  // the GPU arena path through the arena's block table and a second instance of the fused kernel
+  void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
+  bool no_decay_norm_bias() const { return no_decay_; }
   long step_count() const { return t_; }
   void set_step_count(long t) { t_ = t; }
   // a replayed graph ran one step on the device: mirror it on the host (t) and upload a changed
@@ -674,6 +727,7 @@ class Adam : public Optimizer {
  private:
   float b1_, b2_, eps_, wd_;
   bool decoupled_;
+  bool no_decay_ = false;
   long t_ = 0;
   // GPU arena path: step scalars in device memory {lr, bc1, bc2, t}, updated on the device
   Tensor hyper_;

@@ -70,6 +70,14 @@ void relu_mask(const float* dy, const float* y, float* dx, long n);
 void adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float bc1,
           float bc2, float wd, bool decoupled);
 void sgd(float* p, const float* g, float* vel, long n, float lr, float momentum);
+// adam with a weight-decay exclusion: nodecay[(n + 63) / 64], a set byte steps its 64-element block
+// with wd = 0 (a parameter smaller than 64 elements: one byte)
+void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                  float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
+// stochastic depth: mask[n] = 0 or 1 / (1 - p) from (seed, draw), the one function of the kernel
+// library and the native backend; y[n][:] = mask[n] x[n][:] over samples of `row` elements
+void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw);
+void drop_path_scale(const float* x, const float* mask, float* y, long N, long row);
 }  // namespace cpu_ops
 
 namespace gpu_ops {
@@ -302,6 +310,23 @@ void sgd(float* p, const float* g, float* vel, void* shadow, long n, float lr, f
 void adam_hyper_step(float* hyper, float b1, float b2);
 void adam_dev(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2, float eps,
               float wd, bool decoupled, const float* hyper);
+// the same with the weight-decay exclusion: nodecay is a device table of one byte per 64-element block
+void adam_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
+                  float eps, float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
+void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2,
+                      float eps, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay);
+// stochastic depth (droppath.hip, bf16 activations). drop_path_draw: *slot = ++*ctr on the device,
+// then the mask of (seed, *slot) into mask[N] (a captured step draws a new mask at every replay);
+// drop_path_mask: the mask of a given draw index. drop_path_scale: y[n] = mask[n] x[n] (+ residual)
+// over samples of `row` elements. layer_scale_drop_*: the LayerScale with the mask in its residual
+// store, y = residual + mask[n] g[c] x, dx = mask[n] g[c] dy, dg += sum mask[n] dy x (rps rows per sample)
+void drop_path_draw(float* mask, int N, float p, uint64_t seed, uint64_t* ctr, uint64_t* slot);
+void drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw);
+void drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row);
+void layer_scale_drop_fwd(const void* x, const float* g, const float* mask, const void* residual, void* y, long R,
+                          int C, long rps);
+void layer_scale_drop_bwd(const void* dy, const void* x, const float* g, const float* mask, void* dx, float* dg,
+                          long R, int C, long rps);
 // {loss (fp32), -, correct (int32)} of the last fused loss launch (read after a graph replay)
 const void* loss_device();
 }  // namespace gpu_ops

@@ -340,7 +340,9 @@ ImageDataset load_tiny_imagenet(const std::string& root, const std::string& spli
 // ---------------------------------------------------------------- model zoo
 // the reference's builders (include/nn/example_models.hpp): mnist_cnn, cifar10_resnet9,
 // resnet18_tiny_imagenet, resnet34_tiny_imagenet, resnet50_tiny_imagenet
-Sequential create_model(const std::string& name);
+// drop_path_rate: stochastic depth of the ConvNeXt models (the last block's rate, rising linearly
+// from 0); drop_path_seed != 0: block k's DropPath gets the explicit seed drop_path_seed + k
+Sequential create_model(const std::string& name, float drop_path_rate = 0.f, uint64_t drop_path_seed = 0);
 
 // training loop with an optional scheduler stepped once per optimizer step (ReduceLROnPlateau:
 // once per epoch with the validation loss) and a loss of the factory

@@ -133,7 +133,7 @@ void ConvBase::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) 
   // (C, 1, KH, KW): NCHW and NHWC are the same bytes [C][KH][KW]
   const Layout wl = dev.is_gpu() && !depthwise() ? Layout::NHWC : Layout::NCHW;
   add_param("weights", {co_, cig, kh_, kw_}, wl, uniform_init((size_t)co_ * cig * kh_ * kw_, bound, seed));
-  if (bias_) add_param("bias", {co_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)co_, bound, seed + 1));
+  if (bias_) add_param("bias", {co_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)co_, bound, seed + 1)).no_decay = true;
 }
 
 double ConvBase::flops(const std::vector<int64_t>& in) const {
@@ -451,7 +451,7 @@ void Dense::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
   params_.clear();
   const float bound = 1.f / std::sqrt((float)in_);
   add_param("weights", {out_, in_, 1, 1}, Layout::NCHW, uniform_init((size_t)out_ * in_, bound, seed));
-  if (bias_) add_param("bias", {out_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)out_, bound, seed + 1));
+  if (bias_) add_param("bias", {out_, 1, 1, 1}, Layout::NCHW, uniform_init((size_t)out_, bound, seed + 1)).no_decay = true;
 }
 
 // (DCNN_HEAD_FUSE=0: the classifier head as its six separate kernels — test / A-B hook)
@@ -564,8 +564,8 @@ void BatchNorm::build(const std::vector<int64_t>& in, Device dev, uint64_t seed)
   dev_ = dev;
   params_.clear();
   if (affine_) {
-    add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f));
-    add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f));
+    add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f)).no_decay = true;
+    add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f)).no_decay = true;
   }
   running_mean = Tensor::zeros({c_}, DType::F32, dev);
   running_var = Tensor::from_host(std::vector<float>((size_t)c_, 1.f), {c_}, dev);
@@ -846,6 +846,7 @@ static int fuse_kind(const Layer* l) {
   if (dynamic_cast<const Flatten*>(l)) return FK_FLATTEN;
   if (dynamic_cast<const Dense*>(l)) return FK_DENSE;
   if (dynamic_cast<const LayerScale*>(l)) return FK_LSCALE;
+  if (dynamic_cast<const DropPath*>(l)) return FK_DROPPATH;
   return FK_OTHER;
 }
 
@@ -955,8 +956,8 @@ void GroupNorm::build(const std::vector<int64_t>& in, Device dev, uint64_t seed)
   dev_ = dev;
   params_.clear();
   // (the kernels take gamma / beta always: non-affine runs with the identity pair)
-  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f));
-  add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f));
+  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f)).no_decay = true;
+  add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f)).no_decay = true;
   if (!affine_) {
     params_.clear();
     gb_identity_ = true;
@@ -1032,8 +1033,8 @@ void LayerNorm::build(const std::vector<int64_t>& in, Device dev, uint64_t seed)
   dev_ = dev;
   params_.clear();
   if (!affine_) return;
-  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f));
-  add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f));
+  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 1.f)).no_decay = true;
+  add_param("beta", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, 0.f)).no_decay = true;
 }
 
 Tensor LayerNorm::forward(const Tensor& x, bool training) {
@@ -1091,11 +1092,13 @@ void LayerScale::build(const std::vector<int64_t>& in, Device dev, uint64_t seed
   (void)seed;
   dev_ = dev;
   params_.clear();
-  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, init_));
+  add_param("gamma", {c_, 1, 1, 1}, Layout::NCHW, std::vector<float>((size_t)c_, init_)).no_decay = true;
 }
 
-Tensor LayerScale::forward_residual(const Tensor& x, const Tensor* residual, bool training) {
+Tensor LayerScale::forward_residual(const Tensor& x, const Tensor* residual, bool training, const Tensor* mask) {
   (void)training;
+  if (mask != nullptr && (!dev_.is_gpu() || residual == nullptr))
+    throw std::runtime_error(name_ + ": a drop mask needs the GPU path and a residual");
   check_act(x, dev_, "layer_scale");
   if (x.dim(1) != c_) throw std::runtime_error(name_ + ": channel count mismatch");
   if (residual != nullptr && residual->shape() != x.shape())
@@ -1103,11 +1106,14 @@ Tensor LayerScale::forward_residual(const Tensor& x, const Tensor* residual, boo
   const long N = x.dim(0), HW = x.dim(2) * x.dim(3);
   const float* g = params_[0].value.ptr<float>();
   Tensor y = act_empty(x.shape(), dev_);
-  if (dev_.is_gpu())
+  if (mask != nullptr)
+    gpu_ops::layer_scale_drop_fwd(x.data(), g, mask->ptr<float>(), residual->data(), y.data(), N * HW, c_, HW);
+  else if (dev_.is_gpu())
     gpu_ops::layer_scale_fwd(x.data(), g, residual ? residual->data() : nullptr, y.data(), N * HW, c_);
   else
     cpu_ops::layer_scale_fwd(x.ptr<float>(), g, residual ? residual->ptr<float>() : nullptr, y.ptr<float>(), N, c_, HW);
   mbc().a = x;
+  mbc().b = mask != nullptr ? *mask : Tensor();  // the drop tail's mask of this micro-batch
   return y;
 }
 
@@ -1117,10 +1123,81 @@ Tensor LayerScale::backward(const Tensor& dy) {
   const float* g = params_[0].value.ptr<float>();
   float* dg = params_[0].grad.ptr<float>();
   Tensor dx = act_empty(x_.shape(), dev_);
-  if (dev_.is_gpu())
+  if (mbc().b.defined())
+    gpu_ops::layer_scale_drop_bwd(dy.data(), x_.data(), g, mbc().b.ptr<float>(), dx.data(), dg, N * HW, c_, HW);
+  else if (dev_.is_gpu())
     gpu_ops::layer_scale_bwd(dy.data(), x_.data(), g, dx.data(), dg, N * HW, c_);
   else
     cpu_ops::layer_scale_bwd(x_.ptr<float>(), dy.ptr<float>(), g, dx.ptr<float>(), dg, N, c_, HW);
+  return dx;
+}
+
+// ------------------------------------------------------------------ DropPath
+DropPath::DropPath(float rate, std::string name, bool has_seed, uint64_t seed)
+    : Layer(std::move(name)), p_(rate), has_seed_(has_seed), explicit_seed_(seed) {
+  if (!(rate >= 0.f && rate < 1.f)) throw std::runtime_error("drop_path: drop_rate must be in [0, 1)");
+}
+
+json::Value DropPath::parameters_config() const {
+  json::Value p = json::Value::object();
+  p["drop_rate"] = (double)p_;
+  if (has_seed_) p["seed"] = (int64_t)explicit_seed_;
+  return p;
+}
+
+double DropPath::flops(const std::vector<int64_t>& in) const {
+  return 2.0 * (double)in[0] * (double)in[1] * (double)in[2] * (double)in[3];  // one multiply, forward and backward
+}
+
+void DropPath::build(const std::vector<int64_t>& in, Device dev, uint64_t seed) {
+  (void)in;
+  dev_ = dev;
+  seed_ = seed;
+  draws_ = 0;
+  caches_.clear();
+  ctr_ = dev.is_gpu() ? Tensor::zeros({1}, DType::I64, dev) : Tensor();
+}
+
+const Tensor* DropPath::draw_mask(int64_t N, bool training) {
+  MbCache& c = mbc();
+  c.flag = training && p_ > 0.f;
+  if (!c.flag) return nullptr;
+  if (dev_.is_gpu()) {
+    // the mask buffer and the draw-index slot of this micro-batch are created once and kept (a
+    // captured step addresses them)
+    if (!c.a.defined() || c.a.numel() != N) c.a = Tensor::zeros({N}, DType::F32, dev_);
+    if (!c.c.defined()) c.c = Tensor::zeros({1}, DType::I64, dev_);
+    gpu_ops::drop_path_draw(c.a.ptr<float>(), (int)N, p_, mask_seed(), static_cast<uint64_t*>(ctr_.data()),
+                            static_cast<uint64_t*>(c.c.data()));
+  } else {
+    if (!c.a.defined() || c.a.numel() != N) c.a = Tensor::zeros({N}, DType::F32, dev_);
+    cpu_ops::drop_path_mask(c.a.ptr<float>(), N, p_, mask_seed(), ++draws_);
+  }
+  return &c.a;
+}
+
+Tensor DropPath::forward(const Tensor& x, bool training) {
+  check_act(x, dev_, "drop_path");
+  const Tensor* m = draw_mask(x.dim(0), training);
+  if (m == nullptr) return x;
+  const long N = x.dim(0), row = x.numel() / N;
+  Tensor y = act_empty(x.shape(), dev_);
+  if (dev_.is_gpu())
+    gpu_ops::drop_path_scale(x.data(), m->ptr<float>(), nullptr, y.data(), N, row);
+  else
+    cpu_ops::drop_path_scale(x.ptr<float>(), m->ptr<float>(), y.ptr<float>(), N, row);
+  return y;
+}
+
+Tensor DropPath::backward(const Tensor& dy) {
+  MbCache& c = mbc();
+  if (!c.flag) return dy;
+  const long N = dy.dim(0), row = dy.numel() / N;
+  Tensor dx = act_empty(dy.shape(), dev_);
+  if (dev_.is_gpu())
+    gpu_ops::drop_path_scale(dy.data(), c.a.ptr<float>(), nullptr, dx.data(), N, row);
+  else
+    cpu_ops::drop_path_scale(dy.ptr<float>(), c.a.ptr<float>(), dx.ptr<float>(), N, row);
   return dx;
 }
 
@@ -1272,16 +1349,28 @@ LayerScale* ResidualBlock::scale_tail() const {
                               act_ == "none" || act_ == "linear") &
         RF_SCALE_TAIL))
     return nullptr;
-  return static_cast<LayerScale*>(main_.back().get());
+  return static_cast<LayerScale*>(main_[main_.size() - (drop_tail() != nullptr ? 2 : 1)].get());
+}
+
+DropPath* ResidualBlock::drop_tail() const {
+  if (!dev_.is_gpu() ||
+      !(plan_residual_fusions(fuse_kinds(main_), fuse_kinds(short_), act_ == "relu" || act_ == "linear",
+                              act_ == "none" || act_ == "linear") &
+        RF_DROP_TAIL))
+    return nullptr;
+  return static_cast<DropPath*>(main_.back().get());
 }
 
 Tensor ResidualBlock::forward(const Tensor& x, bool training) {
   check_act(x, dev_, "residual_block");
   Tensor& y_ = mbc().a;
   if (LayerScale* ls = scale_tail()) {  // y = x + gamma main(x) in the LayerScale's store
+    // (with a drop tail: y = x + mask[n] gamma main(x), the DropPath draws and the store applies it)
+    DropPath* dp = drop_tail();
+    const size_t nt = dp != nullptr ? 2 : 1;
     Tensor m = x;
-    for (size_t i = 0; i + 1 < main_.size(); ++i) m = main_[i]->forward(m, training);
-    y_ = ls->forward_residual(m, &x, training);
+    for (size_t i = 0; i + nt < main_.size(); ++i) m = main_[i]->forward(m, training);
+    y_ = ls->forward_residual(m, &x, training, dp != nullptr ? dp->draw_mask(x.dim(0), training) : nullptr);
     return y_;
   }
   if (BatchNorm* tail = fused_tail()) {  // y = act(bn(main(x)) + shortcut(x)) in the BN's apply pass
@@ -1323,8 +1412,9 @@ Tensor ResidualBlock::backward(const Tensor& dy) {
   const Tensor& y_ = mbc().a;
   if (scale_tail() != nullptr) {
     // the shortcut gradient is dy itself: the first layer's data gradient adds it in its store
+    // (a drop tail's DropPath has no backward of its own: the LayerScale holds its mask)
     Tensor gm = dy;
-    for (size_t i = main_.size(); i-- > 1;) gm = main_[i]->backward(gm);
+    for (size_t i = main_.size() - (drop_tail() != nullptr ? 1 : 0); i-- > 1;) gm = main_[i]->backward(gm);
     auto* head = dynamic_cast<ConvBase*>(main_[0].get());
     Tensor dx;
     if (head != nullptr && input_grad_ && head->backward_residual(gm, dy, dx)) return dx;
@@ -1598,6 +1688,9 @@ std::unique_ptr<Layer> create_layer(const json::Value& rec) {
   if (type == "layer_scale")
     return std::make_unique<LayerScale>(I("num_channels", 0), (float)p.get_number("init_value", 1e-6), name);
   if (type == "dropout") return std::make_unique<Dropout>((float)p.get_number("dropout_rate", 0.5), name);
+  if (type == "drop_path")
+    return std::make_unique<DropPath>((float)p.get_number("drop_rate", 0.0), name, p.has("seed"),
+                                      (uint64_t)p.get_int("seed", 0));
   if (type == "residual_block") {
     auto path = [&](const char* key) {
       std::vector<std::unique_ptr<Layer>> out;
@@ -1658,6 +1751,15 @@ void Sequential::pack_params() {
     if (p->shadow.defined()) gpu::copy(ns.data(), p->shadow.data(), p->shadow.nbytes(), 2);
     p->shadow = ns;
     p->arena = A;
+  }
+  // the weight-decay exclusion table: one byte per 64-element block (static)
+  {
+    std::vector<uint8_t> tab(A->n / 64, 0);
+    for (size_t k = 0; k < ps.size(); ++k)
+      if (ps[k]->no_decay)
+        for (size_t b = off[k] / 64; b < (off[k] + (size_t)ps[k]->value.numel() + 63) / 64; ++b) tab[b] = 1;
+    A->nodecay = Tensor::empty({(int64_t)tab.size()}, DType::U8, dev_);
+    gpu::copy(A->nodecay.data(), tab.data(), tab.size(), 0);
   }
   // the convs' pre-transposed dgrad operands (from the arena shadows)
   std::vector<Layer*> all;
@@ -2034,7 +2136,8 @@ SequentialBuilder& SequentialBuilder::layer_scale(float init_value, const std::s
 }
 
 // (sub-layer names as the Python LayerBuilder numbers them)
-SequentialBuilder& SequentialBuilder::convnext_block(int channels, float layer_scale_init, const std::string& name) {
+SequentialBuilder& SequentialBuilder::convnext_block(int channels, float layer_scale_init, const std::string& name,
+                                                     float drop_path, bool has_seed, uint64_t drop_path_seed) {
   if (channels != conv_in()) throw std::invalid_argument("convnext_block: channels must match the running shape");
   std::vector<std::unique_ptr<Layer>> m, sc;
   m.push_back(std::make_unique<DepthwiseConv2D>(channels, 7, 7, 1, 1, 3, 3, true, "depthwise_conv2d_0"));
@@ -2043,6 +2146,7 @@ SequentialBuilder& SequentialBuilder::convnext_block(int channels, float layer_s
   m.push_back(std::make_unique<Activation>("gelu", "activation_3"));
   m.push_back(std::make_unique<Conv2D>(4 * channels, channels, 1, 1, 1, 1, 0, 0, true, "conv2d_4"));
   m.push_back(std::make_unique<LayerScale>(channels, layer_scale_init, "layer_scale_5"));
+  if (drop_path > 0.f) m.push_back(std::make_unique<DropPath>(drop_path, "drop_path_6", has_seed, drop_path_seed));
   return residual(std::move(m), std::move(sc), "none",
                   name.empty() ? "convnext_block_" + std::to_string(model_.layers().size()) : name);
 }
@@ -2050,6 +2154,11 @@ SequentialBuilder& SequentialBuilder::convnext_block(int channels, float layer_s
 SequentialBuilder& SequentialBuilder::convnext_downsample(int out_ch, const std::string& name) {
   layernorm(1e-6f, true, name + "_ln");
   return conv2d(out_ch, 2, 2, 2, 2, 0, 0, true, name + "_conv");
+}
+
+SequentialBuilder& SequentialBuilder::drop_path(float rate, const std::string& name) {
+  model_.add(std::make_unique<DropPath>(rate, auto_name(name, "drop_path")));
+  return *this;
 }
 
 SequentialBuilder& SequentialBuilder::dropout(float rate, const std::string& name) {
@@ -2201,8 +2310,13 @@ void Adam::step(const std::vector<Param*>& params) {
     ++t_;
     ++hyper_t_;
     gpu_ops::adam_hyper_step(hyper_.ptr<float>(), b1_, b2_);
-    gpu_ops::adam_dev(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
-                      a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>());
+    if (no_decay_)
+      gpu_ops::adam_dev_nodecay(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
+                                a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>(),
+                                static_cast<const uint8_t*>(a->nodecay.data()));
+    else
+      gpu_ops::adam_dev(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
+                        a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>());
     a->refresh_transposes();
     return;
   }
@@ -2214,12 +2328,13 @@ void Adam::step(const std::vector<Param*>& params) {
       p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
       p->v = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
     }
+    const float wd = no_decay_ && p->no_decay ? 0.f : wd_;  // (per parameter: the flag itself, no table)
     if (p->value.device().is_gpu())
       gpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                    p->shadow.data(), p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd_, decoupled_);
+                    p->shadow.data(), p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
     else
       cpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                    p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd_, decoupled_);
+                    p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
   }
 }
 

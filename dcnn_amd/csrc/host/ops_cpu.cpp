@@ -156,6 +156,19 @@ void adam(float* p, const float* g, float* m, float* v, long n, float lr, float 
   C::adam_step(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0);
 }
 
+void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                  float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay) {
+  C::adam_step_nodecay(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nodecay);
+}
+
+void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw) {
+  C::drop_path_mask(mask, N, p, seed, draw);
+}
+
+void drop_path_scale(const float* x, const float* mask, float* y, long N, long row) {
+  C::drop_path_scale<float>(x, mask, y, N, row);
+}
+
 void sgd(float* p, const float* g, float* vel, long n, float lr, float momentum) {
   C::sgd_step(p, g, vel, n, lr, momentum);
 }

@@ -1169,6 +1169,31 @@ void layer_scale_bwd(const void* dy, const void* x, const float* g, void* dx, fl
   lscale_bwd(kBF16, dy, x, g, dx, dg, R, C, ws, cur());
 }
 
+void layer_scale_drop_fwd(const void* x, const float* g, const float* mask, const void* residual, void* y, long R,
+                          int C, long rps) {
+  ln_check("layer_scale_drop_fwd", R, C);
+  lscale_drop_fwd(kBF16, x, g, mask, residual, y, R, C, rps, cur());
+}
+
+void layer_scale_drop_bwd(const void* dy, const void* x, const float* g, const float* mask, void* dx, float* dg,
+                          long R, int C, long rps) {
+  ln_check("layer_scale_drop_bwd", R, C);
+  float* ws = static_cast<float*>(scratch(LN_WS, (size_t)ln_workspace_bytes(R, C)));
+  lscale_drop_bwd(kBF16, dy, x, g, mask, dx, dg, R, C, rps, ws, cur());
+}
+
+// ---- stochastic depth (droppath.hip)
+void drop_path_draw(float* mask, int N, float p, uint64_t seed, uint64_t* ctr, uint64_t* slot) {
+  counter_bump(ctr, slot, cur());
+  dcnn::drop_path_mask(mask, N, p, seed, 0, slot, cur());
+}
+void drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw) {
+  dcnn::drop_path_mask(mask, N, p, seed, draw, nullptr, cur());
+}
+void drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row) {
+  dcnn::drop_path_scale(kBF16, x, mask, residual, y, N, row, cur());
+}
+
 void softmax_fwd(const void* x, void* y, long rows, int C) { softmax_rows(kBF16, x, y, rows, C, cur()); }
 void softmax_bwd(const void* y, const void* dy, void* dx, long rows, int C) {
   softmax_rows_bwd(kBF16, y, dy, dx, rows, C, cur());
@@ -1190,6 +1215,17 @@ void relu_mask(const void* dy, const void* y, void* dx, long n) {
 void adam(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2, float eps,
           float bc1, float bc2, float wd, bool decoupled) {
   adam_step(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nullptr, cur());
+}
+
+void adam_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
+                  float eps, float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay) {
+  adam_step_nodecay(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nullptr,
+                    nodecay, cur());
+}
+void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2,
+                      float eps, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay) {
+  adam_step_nodecay(p, g, m, v, static_cast<bf16*>(shadow), n, 0.f, b1, b2, eps, 1.f, 1.f, wd, decoupled ? 1 : 0, hyper,
+                    nodecay, cur());
 }
 
 const void* loss_device() { return scratch(LOSS_OUT, 16); }

@@ -64,6 +64,14 @@ void TrainGraph::capture(const Tensor& x, const Tensor& labels) {
   for (BatchNorm* bn : model_.batchnorms())
     for (Tensor* t : {&bn->running_mean, &bn->running_var})
       if (t->defined()) bn0.emplace_back(*t, t->clone());
+  // (and every DropPath's device draw counter: replay k then draws what eager step k draws)
+  {
+    std::vector<Layer*> all;
+    for (auto& l : model_.layers()) l->collect_layers(all);
+    for (Layer* l : all)
+      if (auto* dp = dynamic_cast<DropPath*>(l))
+        if (dp->draw_counter().defined()) bn0.emplace_back(dp->draw_counter(), dp->draw_counter().clone());
+  }
   const long t0 = opt_.step_count();
   auto eager = [&] {
     model_.zero_grad();
@@ -581,7 +589,8 @@ ImageDataset load_tiny_imagenet(const std::string& root, const std::string& spli
 }
 
 // ================================================================= model zoo
-Sequential create_model(const std::string& name) {
+Sequential create_model(const std::string& name, float drop_path_rate, uint64_t drop_path_seed) {
+  if (!(drop_path_rate >= 0.f && drop_path_rate < 1.f)) throw std::invalid_argument("drop_path_rate must be in [0, 1)");
   if (name == "mnist_cnn")
     return SequentialBuilder("mnist_cnn_model").input({1, 28, 28})
         .conv2d(8, 5, 5, 1, 1, 0, 0, true, "conv1").batchnorm(1e-5f, 0.1f, true, "bn1")
@@ -688,13 +697,19 @@ Sequential create_model(const std::string& name) {
     b.input({3, hw, hw}).conv2d(widths[0], patch, patch, patch, patch, 0, 0, true, "stem_conv")
         .layernorm(1e-6f, true, "stem_ln");
     int m = hw / patch;
+    // stochastic depth rising linearly over all blocks in order: block k of L gets rate * k / (L - 1)
+    // (models/zoo.py _convnext, computed in double as there); rate 0 adds no layer
+    const int total = depths[0] + depths[1] + depths[2] + depths[3];
+    int k = 0;
     for (int s = 0; s < 4; ++s) {
       if (s > 0) {
         b.convnext_downsample(widths[s], "down" + std::to_string(s + 1));
         m /= 2;
       }
-      for (int i = 1; i <= depths[s]; ++i)
-        b.convnext_block(widths[s], 1e-6f, "stage" + std::to_string(s + 1) + "_block" + std::to_string(i));
+      for (int i = 1; i <= depths[s]; ++i, ++k)
+        b.convnext_block(widths[s], 1e-6f, "stage" + std::to_string(s + 1) + "_block" + std::to_string(i),
+                         (float)((double)drop_path_rate * k / std::max(total - 1, 1)), drop_path_seed != 0,
+                         drop_path_seed + (uint64_t)k);
     }
     return b.avgpool2d(m, m, 1, 1, 0, 0, "avgpool").layernorm(1e-6f, true, "head_ln").flatten("flatten")
         .dense(tiny ? 200 : 10, true, "fc").build();

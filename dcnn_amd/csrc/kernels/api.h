@@ -292,6 +292,24 @@ void lscale_fwd(int dt, const void* x, const float* gamma, const void* residual,
 // dx = gamma[c] dy; dgamma += sum dy x
 void lscale_bwd(int dt, const void* dy, const void* x, const float* gamma, void* dx, float* dgamma, long R, int C,
                 float* workspace, hipStream_t s);
+// The scale tail with stochastic depth: mask [N] fp32 holds 0 or 1 / (1 - p) per sample, a sample
+// is rows_per_sample consecutive rows (R a multiple of it). y = residual + mask[n] gamma[c] x;
+// dx = mask[n] gamma[c] dy, dgamma += sum mask[n] dy x. A dropped sample copies its residual rows
+// (forward) and gets zeros (backward) without reading x. With a mask of ones the results are
+// bit-identical to lscale_fwd / lscale_bwd. Same supported set as the LayerScale.
+void lscale_drop_fwd(int dt, const void* x, const float* gamma, const float* mask, const void* residual, void* y,
+                     long R, int C, long rows_per_sample, hipStream_t s);
+void lscale_drop_bwd(int dt, const void* dy, const void* x, const float* gamma, const float* mask, void* dx,
+                     float* dgamma, long R, int C, long rows_per_sample, float* workspace, hipStream_t s);
+// Stochastic depth (droppath.hip). mask[n] = u01(Philox(seed + draw * 0x9E3779B97F4A7C15, n / 4)
+// lane n % 4) >= p ? 1 / (1 - p) : 0 for n < N; draw is read from the device word ctr when ctr is
+// set (a counter_bump slot). p outside [0, 1) throws.
+float drop_path_keep_scale(float p);
+void drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw, const uint64_t* ctr, hipStream_t s);
+// y[n][:] = mask[n] x[n][:] (+ residual[n][:]), a sample is `row` contiguous elements (any length);
+// forward and backward alike. x, y and residual must share their address modulo 16.
+void drop_path_scale(int dt, const void* x, const float* mask, const void* residual, void* y, long N, long row,
+                     hipStream_t s);
 
 void maxpool_fwd(int dt, const void* x, void* y, uint8_t* idx, PoolGeom g, hipStream_t s);
 void maxpool_bwd(int dt, const void* dy, const uint8_t* idx, void* dx, PoolGeom g, hipStream_t s);
@@ -356,6 +374,11 @@ void loss_fused(int dt, const void* pred, const float* target, const int64_t* la
                 hipStream_t s);
 void adam_step(float* p, const float* g, float* m, float* v, bf16* shadow, long n, float lr, float b1, float b2,
                float eps, float bc1, float bc2, float wd, int decoupled, const float* hyper, hipStream_t s);
+// adam_step with a weight-decay exclusion: nodecay [(n + 63) / 64] bytes, one per 64-element block
+// of the flat buffer; a non-zero byte takes that block's step with wd = 0
+void adam_step_nodecay(float* p, const float* g, float* m, float* v, bf16* shadow, long n, float lr, float b1, float b2,
+                       float eps, float bc1, float bc2, float wd, int decoupled, const float* hyper,
+                       const uint8_t* nodecay, hipStream_t s);
 void sgd_step(float* p, const float* g, float* vel, bf16* shadow, long n, float lr, float mom, const float* hyper,
               hipStream_t s);
 void adam_scalars(float* hyper, float b1, float b2, hipStream_t s);

@@ -255,7 +255,8 @@ PYBIND11_MODULE(_kernels, m) {
                          {"FK_FLATTEN", FK_FLATTEN}, {"FK_DENSE", FK_DENSE}, {"FF_FUSE_HEAD", FF_FUSE_HEAD},
                          {"RF_FUSED_TAIL", RF_FUSED_TAIL},
                          {"RF_DUAL_SHORTCUT", RF_DUAL_SHORTCUT}, {"FK_LSCALE", FK_LSCALE},
-                         {"RF_SCALE_TAIL", RF_SCALE_TAIL}})
+                         {"RF_SCALE_TAIL", RF_SCALE_TAIL}, {"FK_DROPPATH", FK_DROPPATH},
+                         {"RF_DROP_TAIL", RF_DROP_TAIL}})
     m.attr(name) = v;
   m.def("g1s_rows", &g1s_rows);
   m.def("g1s_enable", &g1s_enable);
@@ -398,6 +399,45 @@ PYBIND11_MODULE(_kernels, m) {
                          uintptr_t ws, uintptr_t st) {
     lscale_bwd(dt, P<const void*>(dy), P<const void*>(x), P<const float*>(gamma), P<void*>(dx), P<float*>(dg), R, C,
                P<float*>(ws), S(st));
+  });
+  m.def("lscale_drop_fwd", [](int dt, uintptr_t x, uintptr_t gamma, uintptr_t mask, uintptr_t residual, uintptr_t y,
+                              long R, int C, long rps, uintptr_t st) {
+    lscale_drop_fwd(dt, P<const void*>(x), P<const float*>(gamma), P<const float*>(mask), P<const void*>(residual),
+                    P<void*>(y), R, C, rps, S(st));
+  });
+  m.def("lscale_drop_bwd", [](int dt, uintptr_t dy, uintptr_t x, uintptr_t gamma, uintptr_t mask, uintptr_t dx,
+                              uintptr_t dg, long R, int C, long rps, uintptr_t ws, uintptr_t st) {
+    lscale_drop_bwd(dt, P<const void*>(dy), P<const void*>(x), P<const float*>(gamma), P<const float*>(mask),
+                    P<void*>(dx), P<float*>(dg), R, C, rps, P<float*>(ws), S(st));
+  });
+  // stochastic depth (droppath.hip)
+  m.def("drop_path_mask_into", [](uintptr_t mask, int N, float p, uint64_t seed, uint64_t draw, uintptr_t ctr,
+                                  uintptr_t st) {
+    drop_path_mask(P<float*>(mask), N, p, seed, draw, P<const uint64_t*>(ctr), S(st));
+  });
+  // the N mask values of (seed, draw) computed on the GPU and returned as a list (tests, tools)
+  m.def("drop_path_mask", [](uint64_t seed, uint64_t draw, int N, float p) {
+    drop_path_keep_scale(p);
+    if (N < 1) throw std::invalid_argument("drop_path_mask: N < 1");
+    auto check = [](hipError_t e) {
+      if (e != hipSuccess) throw std::runtime_error(std::string("drop_path_mask: HIP error ") + hipGetErrorString(e));
+    };
+    float* d = nullptr;
+    check(hipMalloc(&d, (size_t)N * sizeof(float)));
+    std::vector<float> h(N);
+    try {
+      drop_path_mask(d, N, p, seed, draw, nullptr, nullptr);
+      check(hipMemcpy(h.data(), d, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    check(hipFree(d));
+    return h;
+  });
+  m.def("drop_path_scale", [](int dt, uintptr_t x, uintptr_t mask, uintptr_t residual, uintptr_t y, long N, long row,
+                              uintptr_t st) {
+    drop_path_scale(dt, P<const void*>(x), P<const float*>(mask), P<const void*>(residual), P<void*>(y), N, row, S(st));
   });
 
   // depthwise conv (dwconv.hip): geometry as (N, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW)
@@ -615,6 +655,12 @@ PYBIND11_MODULE(_kernels, m) {
                         uintptr_t st) {
     adam_step(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(shadow), n, lr, b1, b2, eps, bc1,
               bc2, wd, dec, P<const float*>(hyper), S(st));
+  });
+  m.def("adam_step_nodecay", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t shadow, long n, float lr,
+                                float b1, float b2, float eps, float bc1, float bc2, float wd, int dec,
+                                uintptr_t hyper, uintptr_t nodecay, uintptr_t st) {
+    adam_step_nodecay(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(shadow), n, lr, b1, b2,
+                      eps, bc1, bc2, wd, dec, P<const float*>(hyper), P<const uint8_t*>(nodecay), S(st));
   });
   m.def("adam_scalars", [](uintptr_t hyper, float b1, float b2, uintptr_t st) {
     adam_scalars(P<float*>(hyper), b1, b2, S(st));

@@ -42,6 +42,10 @@ int plan_residual_fusions(const std::vector<int>& main_kinds, const std::vector<
   // identity shortcut, no activation, main path closing in a LayerScale: x + gamma F(x) in its store
   if (act_identity && short_kinds.empty() && main_kinds.size() >= 2 && main_kinds.back() == FK_LSCALE)
     return RF_SCALE_TAIL;
+  // the same with a DropPath behind the LayerScale: the store also applies the per-sample mask
+  if (act_identity && short_kinds.empty() && main_kinds.size() >= 3 && main_kinds.back() == FK_DROPPATH &&
+      main_kinds[main_kinds.size() - 2] == FK_LSCALE)
+    return RF_SCALE_TAIL | RF_DROP_TAIL;
   // the main path's closing BatchNorm applies the shortcut sum and the block activation
   const bool tail = act_ok && main_kinds.size() >= 2 && main_kinds.back() == FK_BN;
   if (!tail) return 0;

@@ -9,7 +9,7 @@ namespace dcnn {
 // layer kinds in order -> per-layer FF_* flags
 enum FuseKind : int {
   FK_OTHER = 0, FK_CONV = 1, FK_BN = 2, FK_RELU = 3, FK_ACT = 4, FK_MAXPOOL = 5, FK_AVGPOOL = 6, FK_FLATTEN = 7,
-  FK_DENSE = 8, FK_LSCALE = 9
+  FK_DENSE = 8, FK_LSCALE = 9, FK_DROPPATH = 10
 };
 enum FuseFlag : int {
   FF_EMIT_BN_STATS = 1,  // conv: its epilogue emits the statistics rows of the BatchNorm after it
@@ -28,8 +28,11 @@ std::vector<int> plan_sequence_fusions(const std::vector<int>& kinds);
 // RF_DUAL_SHORTCUT = the shortcut's closing BatchNorm shares that pass;
 // RF_SCALE_TAIL = the main path closes in a LayerScale, the shortcut is the identity and the block
 // has no activation (act_identity: none / linear): the LayerScale's store adds the block input,
-// and the first layer's data gradient adds the shortcut gradient (no separate add either way)
-enum ResidualFlag : int { RF_FUSED_TAIL = 1, RF_DUAL_SHORTCUT = 2, RF_SCALE_TAIL = 4 };
+// and the first layer's data gradient adds the shortcut gradient (no separate add either way);
+// RF_DROP_TAIL (always with RF_SCALE_TAIL) = the main path closes in LayerScale, DropPath under the
+// same conditions: that store also applies the DropPath's per-sample mask (lscale_drop_fwd / _bwd).
+// A DropPath anywhere else is FK_OTHER to every rule: the block takes the plain path.
+enum ResidualFlag : int { RF_FUSED_TAIL = 1, RF_DUAL_SHORTCUT = 2, RF_SCALE_TAIL = 4, RF_DROP_TAIL = 8 };
 int plan_residual_fusions(const std::vector<int>& main_kinds, const std::vector<int>& short_kinds, bool act_ok,
                           bool act_identity = false);
 

@@ -25,6 +25,12 @@
 // adds to the gradients (the project's accumulate convention). No float atomics: results are
 // bit-identical from run to run. The grid is capped (2048 workgroups forward, 1024 backward) with
 // a loop over row groups; the slab comes from the caller; nothing here allocates or synchronises.
+//
+// lscale_drop_fwd / lscale_drop_bwd are the LayerScale pair with a stochastic-depth mask (one
+// float per sample, droppath.hip) folded in, for a residual block closing in LayerScale, DropPath
+// (RF_DROP_TAIL): kernels of their own beside lscale_fwd / lscale_bwd, same lane mapping, same slab
+// and reduce. A dropped sample's rows copy the residual (forward) or are zeros (backward) and its
+// x / dy rows are never loaded.
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -293,6 +299,83 @@ __global__ void __launch_bounds__(256) lscale_bwd_kernel(const T* __restrict__ d
   wg_channel_sum<VPL, V, G>(ag, sh, slab + (long)blockIdx.x * C, C);
 }
 
+// The scale tail with stochastic depth: y = res + (mask[n] gamma[c]) x, n the sample of the row
+// (vps vectors per sample). A dropped sample (mask 0) copies its residual rows and never reads x.
+// A kernel of its own: lscale_fwd_kernel keeps its code. With mask = 1 the products are the same
+// operations in the same order, so the bits equal lscale_fwd's.
+template <typename T>
+__global__ void __launch_bounds__(256) lscale_drop_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                              const float* __restrict__ mask,
+                                                              const T* __restrict__ res, T* __restrict__ y, unsigned nv,
+                                                              unsigned nvec, FastDiv vps) {
+  constexpr int V = LnVec<T>::V;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nv; i += gridDim.x * 256u) {
+    const float m = mask[fdiv(i, vps)];
+    float f[V], r[V];
+    LnVec<T>::load(res + (size_t)i * V, r);
+    if (m != 0.f) {
+      const unsigned c = (i % nvec) * V;
+      LnVec<T>::load(x + (size_t)i * V, f);
+#pragma unroll
+      for (int v = 0; v < V; v += 4) {
+        const float4 a = *reinterpret_cast<const float4*>(gamma + c + v);
+        f[v] *= a.x * m; f[v + 1] *= a.y * m; f[v + 2] *= a.z * m; f[v + 3] *= a.w * m;
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) f[v] += r[v];
+      LnVec<T>::store(y + (size_t)i * V, f);
+    } else {
+      LnVec<T>::store(y + (size_t)i * V, r);
+    }
+  }
+}
+
+// dx = (mask[n] gamma[c]) dy; slab row [C] of this workgroup = sum (mask[n] dy) x. A dropped
+// sample's rows are written as zeros and neither dy nor x is read.
+template <typename T, int VPL, int G>
+__global__ void __launch_bounds__(256) lscale_drop_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ mask, T* __restrict__ dx, int R,
+                                                              int C, FastDiv rps, float* __restrict__ slab) {
+  constexpr int V = LnVec<T>::V, RPB = 256 / G;
+  __shared__ __attribute__((aligned(16))) float sh[4 * G * VPL * V];
+  const int g = threadIdx.x % G, sub = threadIdx.x / G;
+  float gm[VPL][V], ag[VPL][V];
+  load_param<VPL, V, G>(gamma, g, C, 1.f, gm);
+#pragma unroll
+  for (int k = 0; k < VPL; ++k)
+#pragma unroll
+    for (int v = 0; v < V; ++v) ag[k][v] = 0.f;
+  for (int row0 = blockIdx.x * RPB; row0 < R; row0 += gridDim.x * RPB) {
+    const int row = row0 + sub;
+    const long base = (long)row * C;
+    const float m = row < R ? mask[fdiv((unsigned)row, rps)] : 0.f;
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+      const int c = (g + k * G) * V;
+      if (row < R && c < C) {
+        float d[V];
+        if (m != 0.f) {
+          float xv[V];
+          LnVec<T>::load(dy + base + c, d);
+          LnVec<T>::load(x + base + c, xv);
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            d[v] *= m;
+            ag[k][v] += d[v] * xv[v];
+            d[v] *= gm[k][v];
+          }
+        } else {
+#pragma unroll
+          for (int v = 0; v < V; ++v) d[v] = 0.f;
+        }
+        LnVec<T>::store(dx + base + c, d);
+      }
+    }
+  }
+  wg_channel_sum<VPL, V, G>(ag, sh, slab + (long)blockIdx.x * C, C);
+}
+
 // out[col] += sum over slab rows of slab[row][col], col < n = parts * C; part p adds into o0 / o1.
 // One workgroup per 16 columns: 16 row slices (slice q owns rows q, q + 16, ...), each summed into 8
 // accumulators (row k of every 8 goes to accumulator k: eight independent loads in flight instead
@@ -430,6 +513,38 @@ void lscale_bwd_t(const void* dy, const void* x, const float* gamma, void* dx, f
   ln_slab_reduce(workspace, grid, 1, C, dgamma, nullptr, s);
 }
 
+template <typename T>
+void lscale_drop_fwd_t(const void* x, const float* gamma, const float* mask, const void* residual, void* y, long R,
+                       int C, long rps, hipStream_t s) {
+  constexpr int V = LnVec<T>::V;
+  const unsigned nv = (unsigned)(R * C / V);
+  const int grid = grid_for(nv, 256, kLnFwdGridCap);
+  lscale_drop_fwd_kernel<T><<<dim3(grid), dim3(256), 0, s>>>((const T*)x, gamma, mask, (const T*)residual, (T*)y, nv,
+                                                            (unsigned)(C / V),
+                                                            make_fastdiv((unsigned)(rps * (C / V))));
+  DCNN_LAUNCH_CHECK();
+}
+
+template <typename T>
+void lscale_drop_bwd_t(const void* dy, const void* x, const float* gamma, const float* mask, void* dx, float* dgamma,
+                       long R, int C, long rps, float* workspace, hipStream_t s) {
+  const int dt = std::is_same<T, bf16>::value ? 1 : 0;
+  const int grid = ln_partial_rows(R, C);
+  ln_dispatch<T>(ln_shape(dt, C), [&](auto vpl, auto g) {
+    lscale_drop_bwd_kernel<T, decltype(vpl)::value, decltype(g)::value><<<dim3(grid), dim3(256), 0, s>>>(
+        (const T*)dy, (const T*)x, gamma, mask, (T*)dx, (int)R, C, make_fastdiv((unsigned)rps), workspace);
+  });
+  DCNN_LAUNCH_CHECK();
+  ln_slab_reduce(workspace, grid, 1, C, dgamma, nullptr, s);
+}
+
+void lscale_drop_check(const char* what, int dt, long R, int C, long rps) {
+  ln_check(what, dt, R, C);
+  if (rps < 1 || R % rps)
+    throw std::invalid_argument(std::string(what) + ": R=" + std::to_string(R) + " rows are not whole samples of " +
+                                std::to_string(rps) + " rows");
+}
+
 }  // namespace lnorm
 using namespace lnorm;
 
@@ -475,6 +590,22 @@ void lscale_bwd(int dt, const void* dy, const void* x, const float* gamma, void*
   if (!dgamma || !workspace) throw std::invalid_argument("lscale_bwd: needs dgamma and a workspace");
   if (dt == 1) lscale_bwd_t<bf16>(dy, x, gamma, dx, dgamma, R, C, workspace, s);
   else lscale_bwd_t<float>(dy, x, gamma, dx, dgamma, R, C, workspace, s);
+}
+
+void lscale_drop_fwd(int dt, const void* x, const float* gamma, const float* mask, const void* residual, void* y,
+                     long R, int C, long rows_per_sample, hipStream_t s) {
+  lscale_drop_check("lscale_drop_fwd", dt, R, C, rows_per_sample);
+  if (!mask || !residual) throw std::invalid_argument("lscale_drop_fwd: needs a mask and a residual");
+  if (dt == 1) lscale_drop_fwd_t<bf16>(x, gamma, mask, residual, y, R, C, rows_per_sample, s);
+  else lscale_drop_fwd_t<float>(x, gamma, mask, residual, y, R, C, rows_per_sample, s);
+}
+
+void lscale_drop_bwd(int dt, const void* dy, const void* x, const float* gamma, const float* mask, void* dx,
+                     float* dgamma, long R, int C, long rows_per_sample, float* workspace, hipStream_t s) {
+  lscale_drop_check("lscale_drop_bwd", dt, R, C, rows_per_sample);
+  if (!mask || !dgamma || !workspace) throw std::invalid_argument("lscale_drop_bwd: needs a mask, dgamma and a workspace");
+  if (dt == 1) lscale_drop_bwd_t<bf16>(dy, x, gamma, mask, dx, dgamma, R, C, rows_per_sample, workspace, s);
+  else lscale_drop_bwd_t<float>(dy, x, gamma, mask, dx, dgamma, R, C, rows_per_sample, workspace, s);
 }
 
 }  // namespace dcnn

@@ -220,6 +220,41 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// adam_kernel with parameters excluded from weight decay: nodecay holds one byte per 64-element
+// block of the flat buffer (arena slices are 64-element aligned, so a block belongs to one
+// parameter); a flagged block takes the step with wd = 0. A kernel of its own: adam_kernel, the
+// launch of every optimizer without the exclusion, keeps its code. The table is static device
+// memory, so a captured step replays it unchanged.
+__global__ void adam_nodecay_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, bf16* __restrict__ shadow, long n, float lr, float b1,
+                                    float b2, float eps, float bc1, float bc2, float wd, int decoupled,
+                                    const float* __restrict__ hyper, const uint8_t* __restrict__ nodecay) {
+  if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; }
+  const long n4 = n / 4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float w = nodecay[i >> 4] ? 0.f : wd;
+    float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    adam1(pp.x, gg.x, mm.x, vv.x, lr, b1, b2, eps, bc1, bc2, w, decoupled);
+    adam1(pp.y, gg.y, mm.y, vv.y, lr, b1, b2, eps, bc1, bc2, w, decoupled);
+    adam1(pp.z, gg.z, mm.z, vv.z, lr, b1, b2, eps, bc1, bc2, w, decoupled);
+    adam1(pp.w, gg.w, mm.w, vv.w, lr, b1, b2, eps, bc1, bc2, w, decoupled);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    if (shadow) {
+      bf16x4 b = {(bf16)pp.x, (bf16)pp.y, (bf16)pp.z, (bf16)pp.w};
+      reinterpret_cast<bf16x4*>(shadow)[i] = b;
+    }
+  }
+  for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float pp = p[i], mm = m[i], vv = v[i];
+    adam1(pp, g[i], mm, vv, lr, b1, b2, eps, bc1, bc2, nodecay[i >> 6] ? 0.f : wd, decoupled);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+    if (shadow) shadow[i] = (bf16)pp;
+  }
+}
+
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ vel,
                            bf16* __restrict__ shadow, long n, float lr, float mom, const float* __restrict__ hyper) {
   if (hyper) lr = hyper[0];
@@ -241,6 +276,15 @@ void adam_step(float* p, const float* g, float* m, float* v, bf16* shadow, long 
                float eps, float bc1, float bc2, float wd, int decoupled, const float* hyper, hipStream_t s) {
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n, lr, b1,
                      b2, eps, bc1, bc2, wd, decoupled, hyper);
+  DCNN_LAUNCH_CHECK();
+}
+
+void adam_step_nodecay(float* p, const float* g, float* m, float* v, bf16* shadow, long n, float lr, float b1, float b2,
+                       float eps, float bc1, float bc2, float wd, int decoupled, const float* hyper,
+                       const uint8_t* nodecay, hipStream_t s) {
+  if (!nodecay) throw std::invalid_argument("adam_step_nodecay: needs the block table ((n + 63) / 64 bytes)");
+  hipLaunchKernelGGL(adam_nodecay_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n,
+                     lr, b1, b2, eps, bc1, bc2, wd, decoupled, hyper, nodecay);
   DCNN_LAUNCH_CHECK();
 }
 

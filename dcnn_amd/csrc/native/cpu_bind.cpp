@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <utility>
+#include <vector>
 
 #include "cpu_kernels.h"
 #include "threadpool.h"
@@ -202,5 +203,21 @@ void bind_cpu(py::module_& parent) {
   m.def("adam_step", [](int dt, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, long n, double lr, double b1,
                         double b2, double eps, double bc1, double bc2, double wd, int dec) {
     DT_DISPATCH(dt, adam_step<T>(P<T>(p), P<const T>(g), P<T>(mm), P<T>(v), n, lr, b1, b2, eps, bc1, bc2, wd, dec));
+  }, Rel());
+  m.def("adam_step_nodecay", [](int dt, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, long n, double lr,
+                                double b1, double b2, double eps, double bc1, double bc2, double wd, int dec,
+                                uintptr_t nodecay) {
+    DT_DISPATCH(dt, adam_step_nodecay<T>(P<T>(p), P<const T>(g), P<T>(mm), P<T>(v), n, lr, b1, b2, eps, bc1, bc2, wd,
+                                         dec, P<const uint8_t>(nodecay)));
+  }, Rel());
+  // the N mask values of stochastic depth for (seed, draw), as a list
+  m.def("drop_path_mask", [](uint64_t seed, uint64_t draw, long N, double p) {
+    if (N < 1) throw std::invalid_argument("drop_path_mask: N < 1");
+    std::vector<float> h((size_t)N);
+    drop_path_mask(h.data(), N, p, seed, draw);
+    return h;
+  });
+  m.def("drop_path_scale", [](int dt, uintptr_t x, uintptr_t mask, uintptr_t y, long N, long row) {
+    DT_DISPATCH(dt, drop_path_scale<T>(P<const T>(x), P<const float>(mask), P<T>(y), N, row));
   }, Rel());
 }

@@ -96,6 +96,14 @@ template <typename T> void sgd_step(T* p, const T* g, T* vel, long n, double lr,
 template <typename T>
 void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
                double bc2, double wd, int decoupled);
+// adam_step, with wd = 0 for every 64-element block whose byte in nodecay [(n + 63) / 64] is set
+template <typename T>
+void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+                       double bc2, double wd, int decoupled, const uint8_t* nodecay);
+// stochastic depth: mask[n] = 0 or 1 / (1 - p), the GPU's mask (csrc/kernels/droppath.hip) bit for
+// bit; y[n][:] = mask[n] x[n][:] over samples of `row` contiguous elements
+void drop_path_mask(float* mask, long N, double p, uint64_t seed, uint64_t draw);
+template <typename T> void drop_path_scale(const T* x, const float* mask, T* y, long N, long row);
 
 }  // namespace cpu
 }  // namespace dcnn_native

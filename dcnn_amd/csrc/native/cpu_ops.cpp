@@ -1001,6 +1001,39 @@ void layer_scale_bwd(const T* x, const T* dy, const T* gamma, T* dx, T* dgamma, 
     });
 }
 
+// ------------------------------------------------------------------ stochastic depth (DropPath)
+// The mask of csrc/kernels/droppath.hip, bit for bit: key seed + draw * 0x9E3779B97F4A7C15,
+// counter n / 4, lane n % 4, kept (scaled by 1 / (1 - p), a float) when u01 >= p.
+void drop_path_mask(float* mask, long N, double p, uint64_t seed, uint64_t draw) {
+  const float pf = (float)p;
+  if (!(pf >= 0.f && pf < 1.f)) throw std::invalid_argument("drop_path_mask: rate is not in [0, 1)");
+  const float keep = 1.0f / (1.0f - pf);
+  const uint64_t key = seed + draw * 0x9E3779B97F4A7C15ull;
+  for (long q = 0; q * 4 < N; ++q) {
+    uint32_t r[4];
+    philox(key, (uint64_t)q, r);
+    for (int k = 0; k < 4; ++k)
+      if (q * 4 + k < N) mask[q * 4 + k] = u01(r[k]) >= pf ? keep : 0.f;
+  }
+}
+
+// y[n][:] = mask[n] x[n][:], a sample is `row` contiguous elements; a dropped sample is not read
+template <typename T>
+void drop_path_scale(const T* x, const float* mask, T* y, long N, long row) {
+  parallel_for(0, N, 1, [&](long lo, long hi) {
+    for (long n = lo; n < hi; ++n) {
+      const T m = (T)mask[n];
+      T* o = y + n * row;
+      if (m == (T)0) {
+        for (long i = 0; i < row; ++i) o[i] = (T)0;
+      } else {
+        const T* r = x + n * row;
+        for (long i = 0; i < row; ++i) o[i] = m * r[i];
+      }
+    }
+  });
+}
+
 // ------------------------------------------------------------------ pooling
 // argmax index = iy * W + ix within the plane (first maximum in window order), -1 for an
 // all-padding window
@@ -1279,6 +1312,29 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
   });
 }
 
+// adam_step with parameters excluded from weight decay: nodecay holds one byte per 64-element
+// block of the flat buffer (arena slices are 64-element aligned); a flagged block steps with wd = 0
+template <typename T>
+void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+                       double bc2, double wd, int decoupled, const uint8_t* nodecay) {
+  for_chunks(n, kGrain, [&](long lo, long hi) {
+    for (long i = lo; i < hi; ++i) {
+      const double w = nodecay[i >> 6] ? 0.0 : wd;
+      const double gi = g[i];
+      m[i] = (T)(b1 * m[i] + (1.0 - b1) * gi);
+      v[i] = (T)(b2 * v[i] + (1.0 - b2) * gi * gi);
+      double upd = lr * (m[i] / bc1) / (std::sqrt(v[i] / bc2) + eps);
+      if (w > 0) {
+        if (decoupled)
+          p[i] -= (T)(w * lr * p[i]);
+        else
+          upd += w * lr * p[i];
+      }
+      p[i] -= (T)upd;
+    }
+  });
+}
+
 // ------------------------------------------------------------------ instantiations
 #define DCNN_CPU_INST(T)                                                                                             \
   template void elementwise<T>(int, int, const T*, const T*, T*, long, double, double);                             \
@@ -1325,7 +1381,10 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
   template void softmax_channels_bwd<T>(const T*, const T*, T*, long, long, long);                                  \
   template double loss_fused<T>(int, const T*, const T*, const int64_t*, T*, long, long, double, long*);            \
   template void sgd_step<T>(T*, const T*, T*, long, double, double);                                                \
-  template void adam_step<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double, int);
+  template void adam_step<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double, int); \
+  template void drop_path_scale<T>(const T*, const float*, T*, long, long);                                          \
+  template void adam_step_nodecay<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double,     \
+                                     double, int, const uint8_t*);
 
 DCNN_CPU_INST(float)
 DCNN_CPU_INST(double)

@@ -233,28 +233,34 @@ def create_resnext26_32x4d_cifar10() -> Sequential:
             .dense(10, True, "fc").build())
 
 
-def _convnext(name, hw, patch, depths, widths, classes) -> Sequential:
+def _convnext(name, hw, patch, depths, widths, classes, drop_path_rate=0.0) -> Sequential:
     """ConvNeXt (Liu et al. 2022): a patchify stem (patch x patch conv, stride = patch) + LayerNorm,
     four stages of ConvNeXt blocks with LayerNorm + 2x2 / stride-2 conv transitions, then average
-    pool -> LayerNorm -> dense. Every bias is on; no stochastic depth."""
+    pool -> LayerNorm -> dense. Every bias is on. ``drop_path_rate``: stochastic depth, rising
+    linearly over all blocks in order (block i of L gets rate * i / (L - 1); a block at rate 0 gets
+    no DropPath layer, so rate 0 is exactly the model without it)."""
+    if not 0.0 <= drop_path_rate < 1.0:
+        raise ValueError(f"drop_path_rate must be in [0, 1), got {drop_path_rate}")
+    total, k = sum(depths), 0
     b = (SequentialBuilder(name).input([3, hw, hw])
          .conv2d(widths[0], patch, patch, patch, patch, 0, 0, True, "stem_conv").layernorm(1e-6, True, "stem_ln"))
     for s, (n, w) in enumerate(zip(depths, widths), 1):
         if s > 1:
             b.convnext_downsample(w, f"down{s}")
         for i in range(1, n + 1):
-            b.convnext_block(w, 1e-6, f"stage{s}_block{i}")
+            b.convnext_block(w, 1e-6, f"stage{s}_block{i}", drop_path_rate * k / max(total - 1, 1))
+            k += 1
     m = b.get_current_shape()[2]
     return (b.avgpool2d(m, m, 1, 1, 0, 0, "avgpool").layernorm(1e-6, True, "head_ln").flatten("flatten")
             .dense(classes, True, "fc").build())
 
 
-def create_convnext_pico_cifar10() -> Sequential:
-    return _convnext("ConvNeXt-Pico-CIFAR10", 32, 2, (2, 2, 6, 2), (64, 128, 256, 512), 10)
+def create_convnext_pico_cifar10(drop_path_rate: float = 0.0) -> Sequential:
+    return _convnext("ConvNeXt-Pico-CIFAR10", 32, 2, (2, 2, 6, 2), (64, 128, 256, 512), 10, drop_path_rate)
 
 
-def create_convnext_tiny_tiny_imagenet() -> Sequential:
-    return _convnext("ConvNeXt-T-Tiny-ImageNet", 64, 4, (3, 3, 9, 3), (96, 192, 384, 768), 200)
+def create_convnext_tiny_tiny_imagenet(drop_path_rate: float = 0.0) -> Sequential:
+    return _convnext("ConvNeXt-T-Tiny-ImageNet", 64, 4, (3, 3, 9, 3), (96, 192, 384, 768), 200, drop_path_rate)
 
 
 MODELS = {
@@ -294,7 +300,8 @@ NUM_CLASSES = {k: (10 if ("cifar" in k or "mnist" in k) else (1000 if k == "resn
                for k in MODELS}
 
 
-def create_model(name: str) -> Sequential:
+def create_model(name: str, **kwargs) -> Sequential:
+    """``kwargs`` go to the model's builder (``drop_path_rate`` for the ConvNeXt models)."""
     if name not in MODELS:
         raise KeyError(f"unknown model {name!r}; available: {sorted(MODELS)}")
-    return MODELS[name]()
+    return MODELS[name](**kwargs)

@@ -7,7 +7,7 @@ from typing import Callable, Dict, List, Optional
 
 from .base import Layer, LayerConfig, ParameterizedLayer, StatelessLayer
 from .conv import Conv2D, Dense, DepthwiseConv2D, GroupedConv2D
-from .misc import Activation, AvgPool2D, Dropout, Flatten, MaxPool2D
+from .misc import Activation, AvgPool2D, DropPath, Dropout, Flatten, MaxPool2D
 from .norm import BatchNorm, GroupNorm, LayerNorm, LayerScale
 from .residual import ResidualBlock, plan_fusion
 
@@ -21,8 +21,8 @@ class LayerFactory:
 
     @classmethod
     def register_defaults(cls) -> None:
-        for L in (Dense, Conv2D, DepthwiseConv2D, GroupedConv2D, Activation, MaxPool2D, AvgPool2D, Dropout, BatchNorm,
-                  GroupNorm, LayerNorm, LayerScale, Flatten, ResidualBlock):
+        for L in (Dense, Conv2D, DepthwiseConv2D, GroupedConv2D, Activation, MaxPool2D, AvgPool2D, Dropout, DropPath,
+                  BatchNorm, GroupNorm, LayerNorm, LayerScale, Flatten, ResidualBlock):
             cls.register_layer(L.type_name, L.from_config)
 
     @classmethod
@@ -133,6 +133,9 @@ class LayerBuilder:
     def dropout(self, dropout_rate, name=""):
         return self.add_layer(Dropout(dropout_rate, self._auto(name, "dropout")))
 
+    def drop_path(self, drop_rate, name="", seed=None):
+        return self.add_layer(DropPath(drop_rate, self._auto(name, "drop_path"), seed))
+
     def flatten(self, name=""):
         return self.add_layer(Flatten(self._auto(name, "flatten")))
 
@@ -146,5 +149,5 @@ def residual_block(main_path, shortcut_path, activation="relu", name="residual_b
 
 
 __all__ = ["Layer", "LayerConfig", "ParameterizedLayer", "StatelessLayer", "Conv2D", "DepthwiseConv2D", "GroupedConv2D", "Dense",
-           "BatchNorm", "GroupNorm", "LayerNorm", "LayerScale", "MaxPool2D", "AvgPool2D", "Dropout", "Flatten", "Activation", "ResidualBlock",
+           "BatchNorm", "GroupNorm", "LayerNorm", "LayerScale", "MaxPool2D", "AvgPool2D", "Dropout", "DropPath", "Flatten", "Activation", "ResidualBlock",
            "LayerFactory", "LayerBuilder", "create_layer", "residual_block", "plan_fusion"]

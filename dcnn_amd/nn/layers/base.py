@@ -185,6 +185,10 @@ class Layer:
         for g in self.gradients():
             g.zero_()
 
+    def step_state(self) -> List[torch.Tensor]:
+        """Device tensors, besides parameters and BatchNorm statistics, that a training step changes."""
+        return []
+
     # ---------------------------------------------------------------- shapes / cost
     def compute_output_shape(self, input_shape: List[int]) -> List[int]:
         return list(input_shape)

@@ -41,7 +41,7 @@ class _ConvBase(ParameterizedLayer):
     def param_specs(self):
         s = [ParamSpec("weights", self._wshape(), self._weights_channels_last)]
         if self.use_bias:
-            s.append(ParamSpec("bias", (self.out_channels, 1, 1, 1)))
+            s.append(ParamSpec("bias", (self.out_channels, 1, 1, 1), no_decay=True))
         return s
 
     def init_values(self, gen):
@@ -329,7 +329,7 @@ class Dense(ParameterizedLayer):
     def param_specs(self):
         s = [ParamSpec("weights", (self.output_features, self.input_features, 1, 1))]
         if self.use_bias:
-            s.append(ParamSpec("bias", (self.output_features, 1, 1, 1)))
+            s.append(ParamSpec("bias", (self.output_features, 1, 1, 1), no_decay=True))
         return s
 
     def init_values(self, gen):

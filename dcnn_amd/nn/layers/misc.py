@@ -1,4 +1,4 @@
-"""Stateless layers: MaxPool2D, AvgPool2D, Dropout, Flatten, Activation.
+"""Stateless layers: MaxPool2D, AvgPool2D, Dropout, DropPath, Flatten, Activation.
 
 Reference: `maxpool2d_layer.tpp`, `avgpool2d_layer.tpp`, `dropout_layer.tpp`,
 `flatten_layer.tpp`, `activation_layer.tpp`. Semantics kept: max-pool ties -> first element,
@@ -8,6 +8,7 @@ implicit -inf padding, stride 0 -> pool size; avg-pool divides by the full windo
 from __future__ import annotations
 
 import random
+from typing import Optional
 
 import torch
 
@@ -189,6 +190,135 @@ class Dropout(StatelessLayer):
     @staticmethod
     def from_config(cfg):
         return Dropout(cfg.parameters["dropout_rate"], cfg.name or "dropout")
+
+
+class DropPath(StatelessLayer):
+    """Stochastic depth (Huang et al. 2016): in training every sample n of the batch is scaled by
+    ``m[n]``, 0 with probability ``drop_rate`` and ``1 / (1 - drop_rate)`` otherwise; the backward
+    scales the gradient by the same mask. Eval mode and rate 0 are the identity (no kernel, no copy).
+
+    ``m`` is one function of (seed, draw, n) — ``drop_path_mask`` in the kernel library, the native
+    CPU backend and the C ABI return the same floats — where ``draw`` counts this layer's training
+    forwards from 1 and the seed is ``seed`` when given (it is then part of the JSON config, so a
+    checkpoint draws the same masks in either front end), else the one from ``set_seed``. GPU
+    (droppath.hip): the mask is written once per forward into a per-micro-batch device buffer that
+    the backward reads; the draw index lives on the device and is bumped in-stream, so a captured
+    step draws a new mask at every replay. Closing a residual block behind a LayerScale, the mask
+    is applied by the LayerScale's store instead (RF_DROP_TAIL in the shared planner)."""
+    type_name = "drop_path"
+
+    def __init__(self, drop_rate: float, name: str = "drop_path", seed: Optional[int] = None):
+        super().__init__(name)
+        if not 0.0 <= drop_rate < 1.0:
+            raise ValueError(f"DropPath '{name}': drop_rate must be in [0, 1), got {drop_rate}")
+        self.drop_rate = float(drop_rate)
+        self.explicit_seed = None if seed is None else int(seed)
+        self._random_seed = random.getrandbits(62)  # without set_seed / an explicit seed
+        self._draws = 0        # CPU: training forwards so far (the draw index of the last one)
+        self._dev_ctr = None   # GPU: the same counter on the device, advanced in-stream
+        self._slots = {}       # mb_id -> 1-element device tensor holding that forward's draw index
+        self._masks = {}       # mb_id -> the last mask of that micro-batch (fp32 [N])
+
+    def mask_seed(self) -> int:
+        if self.explicit_seed is not None:
+            return self.explicit_seed
+        return self.seed if self.use_seed else self._random_seed
+
+    def active(self) -> bool:
+        return self.training and self.drop_rate > 0.0
+
+    def last_mask(self, mb_id: int = 0) -> torch.Tensor:
+        """The mask of micro-batch ``mb_id``'s last training forward (fp32 [N], a copy)."""
+        if mb_id not in self._masks:
+            raise RuntimeError(f"DropPath '{self.name}': no mask drawn for micro-batch {mb_id}")
+        return self._masks[mb_id].clone()
+
+    def _ensure_counter(self, device) -> torch.device:
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._dev_ctr is None or self._dev_ctr.device != device:
+            self._dev_ctr = torch.zeros(1, dtype=torch.int64, device=device)
+            self._slots, self._masks = {}, {}
+        return device
+
+    def step_state(self):
+        """The device draw counter: a training step advances it, so a step runner that rolls its
+        warm-up steps back (runtime/step.py) rolls it back with the weights."""
+        if not self.device.is_gpu():
+            return []
+        self._ensure_counter(self.device.torch_device)
+        return [self._dev_ctr]
+
+    def draw_mask(self, n: int, mb_id: int, device: torch.device) -> Optional[torch.Tensor]:
+        """Draw the next mask for ``n`` samples into micro-batch ``mb_id``'s buffer and return it
+        (None when the layer is the identity). Called by ``forward`` and by a residual block's
+        fused drop tail."""
+        if not self.active():
+            return None
+        if device.type == "cuda":
+            from ...ops import hip
+            device = self._ensure_counter(device)
+            slot = self._slots.get(mb_id)
+            if slot is None:
+                slot = self._slots[mb_id] = torch.zeros(1, dtype=torch.int64, device=device)
+            mask = self._masks.get(mb_id)
+            if mask is None or mask.numel() != n or mask.device != device:
+                mask = self._masks[mb_id] = torch.zeros(n, dtype=torch.float32, device=device)
+            hip.counter_bump(self._dev_ctr, slot)
+            return hip.drop_path_mask(mask, self.drop_rate, self.mask_seed(), slot=slot)
+        from ...ops import cpu
+        self._draws += 1
+        mask = self._masks[mb_id] = cpu.drop_path_mask(self.mask_seed(), self._draws, n, self.drop_rate)
+        return mask
+
+    def forward(self, x, mb_id=0):
+        x = self._to_layer_device(x)
+        if not self.active():
+            self._cache[mb_id] = None
+            return x
+        if x.is_cuda:
+            from ...ops import hip
+            xa = hip.to_act(x, self.compute_dtype) if x.dim() == 4 else x.to(self.compute_dtype).contiguous()
+            mask = self.draw_mask(xa.shape[0], mb_id, xa.device)
+            self._cache[mb_id] = mask
+            return hip.drop_path_scale(xa, mask)
+        from ...ops import cpu
+        mask = self.draw_mask(x.shape[0], mb_id, x.device)
+        self._cache[mb_id] = mask
+        return cpu.drop_path_scale(x, mask)
+
+    def backward(self, grad, mb_id=0):
+        mask = self._cache.pop(mb_id, None)
+        if mask is None:
+            return grad
+        if mask.is_cuda:
+            from ...ops import hip
+            g = grad.to(mask.device)
+            g = hip.to_act(g, self.compute_dtype) if g.dim() == 4 else g.to(self.compute_dtype).contiguous()
+            return hip.drop_path_scale(g, mask)
+        from ...ops import cpu
+        return cpu.drop_path_scale(grad.to(self.compute_dtype), mask)
+
+    def forward_flops(self, s):
+        n = 1
+        for d in s:
+            n *= d
+        return n  # one multiply per element
+
+    def backward_flops(self, s):
+        return self.forward_flops(s)
+
+    def get_config(self):
+        p = dict(drop_rate=self.drop_rate)
+        if self.explicit_seed is not None:
+            p["seed"] = self.explicit_seed
+        return LayerConfig(self.name, p, self.type_name)
+
+    @staticmethod
+    def from_config(cfg):
+        p = cfg.parameters
+        return DropPath(p["drop_rate"], cfg.name or "drop_path", p.get("seed"))
 
 
 class Flatten(StatelessLayer):

@@ -44,7 +44,8 @@ class BatchNorm(ParameterizedLayer):
     def param_specs(self):
         if not self.affine:
             return []
-        return [ParamSpec("gamma", (self.num_features, 1, 1, 1)), ParamSpec("beta", (self.num_features, 1, 1, 1))]
+        return [ParamSpec("gamma", (self.num_features, 1, 1, 1), no_decay=True),
+                ParamSpec("beta", (self.num_features, 1, 1, 1), no_decay=True)]
 
     def init_values(self, gen):
         if not self.affine:
@@ -253,7 +254,8 @@ class GroupNorm(ParameterizedLayer):
     def param_specs(self):
         if not self.affine:
             return []
-        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1)), ParamSpec("beta", (self.num_channels, 1, 1, 1))]
+        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1), no_decay=True),
+                ParamSpec("beta", (self.num_channels, 1, 1, 1), no_decay=True)]
 
     def init_values(self, gen):
         if not self.affine:
@@ -334,7 +336,8 @@ class LayerNorm(ParameterizedLayer):
     def param_specs(self):
         if not self.affine:
             return []
-        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1)), ParamSpec("beta", (self.num_channels, 1, 1, 1))]
+        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1), no_decay=True),
+                ParamSpec("beta", (self.num_channels, 1, 1, 1), no_decay=True)]
 
     def init_values(self, gen):
         if not self.affine:
@@ -410,7 +413,9 @@ class LayerNorm(ParameterizedLayer):
 class LayerScale(ParameterizedLayer):
     """Learnable per-channel scale ``y = gamma[c] * x`` (the layer scale of a ConvNeXt / CaiT
     residual branch). ``forward(x, mb_id, residual=r)`` returns ``r + gamma * x`` from the same
-    store (a residual block's scale tail, RF_SCALE_TAIL in the shared planner)."""
+    store (a residual block's scale tail, RF_SCALE_TAIL in the shared planner); with ``drop_mask``
+    (fp32 [N], a DropPath's mask: RF_DROP_TAIL) it returns ``r + drop_mask[n] * gamma * x`` and the
+    backward applies the same mask (GPU only: lscale_drop_fwd / lscale_drop_bwd in lnorm.hip)."""
     type_name = "layer_scale"
 
     def __init__(self, num_channels: int, init_value: float = 1e-6, name: str = "layer_scale"):
@@ -419,7 +424,7 @@ class LayerScale(ParameterizedLayer):
         self.init_value = float(init_value)
 
     def param_specs(self):
-        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1))]
+        return [ParamSpec("gamma", (self.num_channels, 1, 1, 1), no_decay=True)]
 
     def init_values(self, gen):
         return [torch.full((self.num_channels, 1, 1, 1), self.init_value)]
@@ -431,10 +436,17 @@ class LayerScale(ParameterizedLayer):
 
     _gpu_act = LayerNorm._gpu_act
 
-    def forward(self, x, mb_id=0, residual=None):
+    def forward(self, x, mb_id=0, residual=None, drop_mask=None):
         x = self._to_layer_device(x)
         self._check(x)
         gamma = self._params[0].view(-1)
+        if drop_mask is not None:
+            if not x.is_cuda or residual is None:
+                raise ValueError(f"LayerScale '{self.name}': a drop mask needs the GPU path and a residual")
+            from ...ops import hip
+            xa = self._gpu_act(x)
+            self._cache[mb_id] = (xa, drop_mask)
+            return hip.lscale_drop_fwd(xa, gamma, drop_mask, self._gpu_act(residual))
         if x.is_cuda:
             from ...ops import hip
             xa = self._gpu_act(x)
@@ -449,6 +461,10 @@ class LayerScale(ParameterizedLayer):
         if x is None:
             raise RuntimeError(f"LayerScale '{self.name}': no cached data for micro-batch {mb_id}")
         gamma, dg = self._params[0].view(-1), self._grads[0].view(-1)
+        if isinstance(x, tuple):  # the drop tail: (x, the DropPath's mask of this micro-batch)
+            from ...ops import hip
+            x, mask = x
+            return hip.lscale_drop_bwd(self._gpu_act(grad.to(x.device)), x, gamma, mask, dg)
         if x.is_cuda:
             from ...ops import hip
             return hip.lscale_bwd(self._gpu_act(grad.to(x.device)), x, gamma, dg)

@@ -5,7 +5,9 @@ in the same pass (no pre-activation tensor, no separate add/ReLU kernels), its b
 the ReLU-masked gradient once for both branches, and the branch sum ``dF + dS`` is fused into
 the epilogue of the first conv's dgrad GEMM. A block whose main path closes in a LayerScale, with
 an identity shortcut and no activation (ConvNeXt), takes the scale tail: the LayerScale's store
-writes ``x + gamma * F(x)`` and the first layer's data gradient adds the shortcut gradient.
+writes ``x + gamma * F(x)`` and the first layer's data gradient adds the shortcut gradient. With a
+DropPath behind that LayerScale (the drop tail) the same store applies the per-sample mask:
+``x + m[n] * gamma * F(x)``. A DropPath anywhere else runs as its own kernel on the plain path.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ import torch
 from ..activations import ActivationFactory
 from .base import LayerConfig, Layer, run_backward
 from .conv import Conv2D, DepthwiseConv2D, GroupedConv2D
-from .misc import Activation, MaxPool2D
+from .misc import Activation, DropPath, MaxPool2D
 from .norm import BatchNorm, LayerScale
 
 
@@ -37,6 +39,8 @@ def fuse_kinds(layers: List[Layer]) -> List[int]:
             out.append(K.FK_MAXPOOL)
         elif isinstance(l, LayerScale):
             out.append(K.FK_LSCALE)
+        elif isinstance(l, DropPath):
+            out.append(K.FK_DROPPATH)
         else:
             out.append(K.FK_OTHER)
     return out
@@ -84,7 +88,7 @@ class ResidualBlock(Layer):
         self.shortcut_path = list(shortcut_path or [])
         self.activation_type = activation
         self.act = ActivationFactory.create(activation)
-        self._fused = self._dual = self._scale_tail = False
+        self._fused = self._dual = self._scale_tail = self._drop_tail = False
 
     # structure -------------------------------------------------------------------------
     def sublayers(self) -> List[Layer]:
@@ -137,7 +141,7 @@ class ResidualBlock(Layer):
         plan_fusion(self.main_path, on_gpu)
         plan_fusion(self.shortcut_path, on_gpu)
         act_ok = self.activation_type in ("relu", "none", "linear")
-        self._fused = self._dual = self._scale_tail = False
+        self._fused = self._dual = self._scale_tail = self._drop_tail = False
         if on_gpu:  # the shared planner's residual rules (fusion_plan.cpp, plan_residual_fusions)
             from ...ops._ext import kernels
             K = kernels()
@@ -146,6 +150,7 @@ class ResidualBlock(Layer):
             self._fused = bool(rf & K.RF_FUSED_TAIL)
             self._dual = bool(rf & K.RF_DUAL_SHORTCUT)
             self._scale_tail = bool(rf & K.RF_SCALE_TAIL)
+            self._drop_tail = bool(rf & K.RF_DROP_TAIL)
         if self._fused:
             self.main_path[-1].emit_masked_grad = True
         for l in self.sublayers():
@@ -186,9 +191,12 @@ class ResidualBlock(Layer):
             from ...ops import hip
             xa = hip.to_act(x, self.compute_dtype)
             h = xa
-            for l in self.main_path[:-1]:
+            nt = 2 if self._drop_tail else 1  # layers of the tail: LayerScale [, DropPath]
+            for l in self.main_path[:-nt]:
                 h = l.forward(h, mb_id)
-            out = self.main_path[-1].forward(h, mb_id, residual=xa)  # x + gamma * F(x) in one store
+            mask = self.main_path[-1].draw_mask(xa.shape[0], mb_id, xa.device) if self._drop_tail else None
+            # x + [m[n] *] gamma * F(x) in one store
+            out = self.main_path[-nt].forward(h, mb_id, residual=xa, drop_mask=mask)
             self._cache[mb_id] = ("scale", None)
             return out
         h = x
@@ -235,8 +243,9 @@ class ResidualBlock(Layer):
             return first.backward(g, mb_id) + d_s
         if kind == "scale":
             # the shortcut gradient is `grad` itself: the first layer's data gradient adds it
+            # (a drop tail's DropPath has no backward of its own: the LayerScale holds its mask)
             g = grad
-            for k in range(len(self.main_path) - 1, 0, -1):
+            for k in range(len(self.main_path) - (2 if self._drop_tail else 1), 0, -1):
                 g = run_backward(self.main_path, k, g, mb_id)
             first = self.main_path[0]
             if not self.needs_input_grad:

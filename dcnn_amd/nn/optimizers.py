@@ -52,18 +52,29 @@ class Optimizer:
         self.params: List[torch.Tensor] = []
         self.grads: List[torch.Tensor] = []
         self.arena = None
+        self.no_decay: Optional[List[bool]] = None
         self._flat_p = self._flat_g = None
         self._hyper = None
         self._hyper_dirty = True  # device scalars must be (re)uploaded before the next step
 
-    def attach(self, params, grads=None, arena=None) -> None:
+    def attach(self, params, grads=None, arena=None, no_decay=None) -> None:
+        """``no_decay``: one bool per parameter, True for those excluded from weight decay (biases,
+        norm affines, layer scales — each layer classes its own, ``ParamSpec.no_decay``). Taken
+        from the model or the arena when one is given."""
         if grads is None and hasattr(params, "parameters"):
             model = params
             params, grads = model.parameters(), model.gradients()
             arena = getattr(model, "arena", None)
+            if no_decay is None and hasattr(model, "no_decay_flags"):
+                no_decay = model.no_decay_flags()
         self.params, self.grads = list(params), list(grads)
         if len(self.params) != len(self.grads):
             raise ValueError("params/grads length mismatch")
+        if no_decay is None and arena is not None and len(arena.specs) == len(self.params):
+            no_decay = arena.no_decay_flags()
+        if no_decay is not None and len(no_decay) != len(self.params):
+            raise ValueError("params/no_decay length mismatch")
+        self.no_decay = None if no_decay is None else [bool(f) for f in no_decay]
         self.arena = arena
         if self.arena is not None:
             ptrs = [p.data_ptr() for p in self.params]
@@ -210,8 +221,13 @@ class SGD(Optimizer):
 
 class Adam(Optimizer):
     def __init__(self, learning_rate: float = 0.001, beta1: float = 0.9, beta2: float = 0.999,
-                 epsilon: float = 1e-8, weight_decay: float = 0.0, decouple_weight_decay: bool = False):
+                 epsilon: float = 1e-8, weight_decay: float = 0.0, decouple_weight_decay: bool = False,
+                 no_decay_norm_bias: bool = False):
+        """``no_decay_norm_bias``: biases, norm affines and layer scales take the step without
+        weight decay. On the fused arena path a static device table of one byte per 64-element
+        block selects them inside the one launch; off (the default), the launch is unchanged."""
         super().__init__(learning_rate)
+        self.no_decay_norm_bias = bool(no_decay_norm_bias)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
         self.weight_decay = float(weight_decay)
         self.decouple_weight_decay = bool(decouple_weight_decay)
@@ -226,6 +242,13 @@ class Adam(Optimizer):
             self.m = [torch.zeros_like(p) for p in self.params]
             self.v = [torch.zeros_like(p) for p in self.params]
         self.t = 0
+        self._nodecay_blocks = None
+        if self.no_decay_norm_bias:
+            if self.no_decay is None:
+                raise ValueError("no_decay_norm_bias needs to know which parameters are biases, norm affines or "
+                                 "layer scales: attach a model or an arena, or pass no_decay=[...]")
+            if self.arena is not None:
+                self._nodecay_blocks = self.arena.no_decay_blocks()
 
     def fused(self) -> bool:
         return self.arena is not None and self._flat_p.is_cuda
@@ -250,7 +273,7 @@ class Adam(Optimizer):
         bc1, bc2 = self._bc
         hip.adam_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate,
                       self.beta1, self.beta2, self.epsilon, bc1, bc2, self.weight_decay,
-                      self.decouple_weight_decay, self._hyper)
+                      self.decouple_weight_decay, self._hyper, nodecay=self._nodecay_blocks)
         self.arena.mark_synced()
 
     def update(self):
@@ -263,8 +286,12 @@ class Adam(Optimizer):
         bc2 = 1.0 - self.beta2 ** self.t
         if self.arena is not None and not self._flat_p.is_cuda:
             from ..ops import cpu   # native flat-buffer step (CPU arena, float32 or float64)
-            cpu.adam_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1,
-                          self.beta2, self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay)
+            args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1, self.beta2,
+                    self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay)
+            if self._nodecay_blocks is not None:
+                cpu.adam_step_nodecay(*args, self._nodecay_blocks)
+            else:
+                cpu.adam_step(*args)
             self.arena.sync_shadow()
             return
         pairs = [(self._flat_p, self._flat_g)] if self.arena is not None else list(zip(self.params, self.grads))
@@ -274,11 +301,12 @@ class Adam(Optimizer):
                 m.mul_(self.beta1).add_((1 - self.beta1) * g)
                 v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
                 upd = self.learning_rate * (m / bc1) / (torch.sqrt(v / bc2) + self.epsilon)
-                if self.weight_decay > 0:
+                wd = 0.0 if (self.no_decay_norm_bias and self.arena is None and self.no_decay[i]) else self.weight_decay
+                if wd > 0:
                     if self.decouple_weight_decay:
-                        p.sub_(self.weight_decay * self.learning_rate * p)
+                        p.sub_(wd * self.learning_rate * p)
                     else:
-                        upd = upd + self.weight_decay * self.learning_rate * p
+                        upd = upd + wd * self.learning_rate * p
                 p.sub_(upd)
         if self.arena is not None:
             self.arena.sync_shadow()
@@ -291,11 +319,12 @@ class Adam(Optimizer):
         return OptimizerConfig(t, self.name(), dict(learning_rate=self.learning_rate, beta1=self.beta1,
                                                     beta2=self.beta2, epsilon=self.epsilon,
                                                     weight_decay=self.weight_decay,
-                                                    decouple_weight_decay=self.decouple_weight_decay))
+                                                    decouple_weight_decay=self.decouple_weight_decay,
+                                                    no_decay_norm_bias=self.no_decay_norm_bias))
 
     def clone(self):
         return Adam(self.learning_rate, self.beta1, self.beta2, self.epsilon, self.weight_decay,
-                    self.decouple_weight_decay)
+                    self.decouple_weight_decay, self.no_decay_norm_bias)
 
     def state_dict(self):
         return {"t": self.t, "m": [x.detach().cpu() for x in self.m or []], "v": [x.detach().cpu() for x in self.v or []]}
@@ -310,8 +339,9 @@ class Adam(Optimizer):
 
 
 class AdamW(Adam):
-    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=0.01):
-        super().__init__(learning_rate, beta1, beta2, epsilon, weight_decay, True)
+    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=0.01,
+                 no_decay_norm_bias=False):
+        super().__init__(learning_rate, beta1, beta2, epsilon, weight_decay, True, no_decay_norm_bias)
 
 
 class OptimizerFactory:
@@ -326,5 +356,5 @@ class OptimizerFactory:
         if t in ("adam", "adamw"):
             return Adam(p.get("learning_rate", 0.001), p.get("beta1", 0.9), p.get("beta2", 0.999),
                         p.get("epsilon", 1e-8), p.get("weight_decay", 0.0),
-                        p.get("decouple_weight_decay", t == "adamw"))
+                        p.get("decouple_weight_decay", t == "adamw"), p.get("no_decay_norm_bias", False))
         raise ValueError(f"Unknown optimizer type: {t}")

@@ -23,6 +23,9 @@ class ParamSpec:
     name: str
     shape: Tuple[int, ...]
     channels_last: bool = False
+    # excluded from weight decay when the optimizer's no_decay_norm_bias is on: set by the owning
+    # layer for biases, norm affines and layer scales (by kind, never by shape)
+    no_decay: bool = False
 
 
 def _strides(shape, channels_last):
@@ -81,6 +84,24 @@ class ParamArena:
 
     def shadow_view(self, i):
         return None if self.shadow is None else self._view(self.shadow, i)
+
+    def no_decay_flags(self) -> List[bool]:
+        return [bool(s.no_decay) for s in self.specs]
+
+    def no_decay_blocks(self) -> torch.Tensor:
+        """One uint8 per ALIGN-element block of the flat buffers, 1 where the block belongs to a
+        parameter excluded from weight decay (slices are ALIGN-aligned, so a block has one owner).
+        On the arena's device; built once and cached: it never changes, so a captured optimizer
+        step replays it as it is."""
+        t = getattr(self, "_no_decay_blocks", None)
+        if t is None:
+            host = torch.zeros(self.numel // ALIGN, dtype=torch.uint8)
+            ends = self.offsets[1:] + [self.numel]
+            for s, lo, hi in zip(self.specs, self.offsets, ends):
+                if s.no_decay:
+                    host[lo // ALIGN:hi // ALIGN] = 1
+            t = self._no_decay_blocks = host.to(self.device)
+        return t
 
     def zero_grad(self):
         if self.grad.is_cuda:

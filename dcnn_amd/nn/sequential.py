@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from ..device import Device, DeviceType, get_cpu, get_device
-from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten, GroupNorm,
+from .layers import (Activation, AvgPool2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, DropPath, Dropout, Flatten, GroupNorm,
                      GroupedConv2D, Layer, LayerBuilder, LayerConfig, LayerFactory, LayerNorm, LayerScale, MaxPool2D,
                      ParameterizedLayer, ResidualBlock, create_layer, plan_fusion)
 from .layers.base import run_backward
@@ -294,6 +294,12 @@ class Sequential:
     def gradients(self, part: Optional[Partition] = None) -> List[torch.Tensor]:
         layers = self.layers if part is None else self.layers[part.start_layer:part.end_layer]
         return [g for l in layers for g in l.gradients()]
+
+    def no_decay_flags(self, part: Optional[Partition] = None) -> List[bool]:
+        """One bool per entry of :meth:`parameters`: True for a parameter its layer keeps out of
+        weight decay (bias, norm affine, layer scale; ``ParamSpec.no_decay``)."""
+        layers = self.layers if part is None else self.layers[part.start_layer:part.end_layer]
+        return [bool(s.no_decay) for l in _leaf_param_layers(layers) for s in l.param_specs()]
 
     def clear_gradients(self) -> None:
         if self.arena is not None:
@@ -704,6 +710,9 @@ class SequentialBuilder:
     def dropout(self, dropout_rate, name=""):
         return self._add(Dropout(dropout_rate, self._n(name, "dropout")))
 
+    def drop_path(self, drop_rate, name="", seed=None):
+        return self._add(DropPath(drop_rate, self._n(name, "drop_path"), seed))
+
     def flatten(self, name=""):
         return self._add(Flatten(self._n(name, "flatten")))
 
@@ -774,18 +783,22 @@ class SequentialBuilder:
     def layer_scale(self, init_value=1e-6, name=""):
         return self._add(LayerScale(self._shape[1], init_value, self._n(name, "layer_scale")))
 
-    def convnext_block(self, channels, layer_scale_init=1e-6, name="convnext_block"):
-        """ConvNeXt block (Liu et al. 2022): x + LayerScale(1x1(GELU(1x1(LayerNorm(dw7x7(x)))))), an
-        identity-shortcut residual block without activation (the scale tail on the GPU)."""
+    def convnext_block(self, channels, layer_scale_init=1e-6, name="convnext_block", drop_path=0.0,
+                       drop_path_seed=None):
+        """ConvNeXt block (Liu et al. 2022): x + DropPath(LayerScale(1x1(GELU(1x1(LayerNorm(dw7x7(x))))))),
+        an identity-shortcut residual block without activation (the scale tail on the GPU, with
+        the stochastic-depth mask in the same store). ``drop_path`` = 0 adds no DropPath layer."""
         shape = [channels, self._shape[2], self._shape[3]]
-        main = (LayerBuilder().input(shape)
-                .depthwise_conv2d(7, 7, 1, 1, 3, 3, True)
-                .layernorm(1e-6, True)
-                .conv2d(4 * channels, 1, 1, 1, 1, 0, 0, True)
-                .activation("gelu")
-                .conv2d(channels, 1, 1, 1, 1, 0, 0, True)
-                .layer_scale(layer_scale_init)
-                .build())
+        lb = (LayerBuilder().input(shape)
+              .depthwise_conv2d(7, 7, 1, 1, 3, 3, True)
+              .layernorm(1e-6, True)
+              .conv2d(4 * channels, 1, 1, 1, 1, 0, 0, True)
+              .activation("gelu")
+              .conv2d(channels, 1, 1, 1, 1, 0, 0, True)
+              .layer_scale(layer_scale_init))
+        if drop_path > 0.0:
+            lb.drop_path(drop_path, seed=drop_path_seed)
+        main = lb.build()
         return self._add(ResidualBlock(main, [], "none", name))
 
     def convnext_downsample(self, out_channels, name="convnext_downsample"):

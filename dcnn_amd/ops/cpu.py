@@ -494,3 +494,30 @@ def sgd_step(p_, g, vel, lr, momentum):
 def adam_step(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, decoupled):
     C().adam_step(dt(p_), p_.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p_.numel(), float(lr), float(b1),
                   float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled))
+
+
+def adam_step_nodecay(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, decoupled, nodecay):
+    """:func:`adam_step` with ``wd = 0`` for every 64-element block of the flat buffer whose byte in
+    ``nodecay`` (uint8, ``ceil(n / 64)`` entries) is set."""
+    if nodecay.dtype != torch.uint8 or not nodecay.is_contiguous() or nodecay.numel() * 64 < p_.numel():
+        raise ValueError("adam_step_nodecay: the block table is uint8 with one entry per 64 elements")
+    C().adam_step_nodecay(dt(p_), p_.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p_.numel(), float(lr),
+                          float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled),
+                          nodecay.data_ptr())
+
+
+def drop_path_mask(seed: int, draw: int, n: int, p_drop: float) -> torch.Tensor:
+    """The stochastic-depth mask of (seed, draw): ``n`` float32 values, 0 or 1 / (1 - p). The same
+    function as the GPU kernel's (csrc/kernels/droppath.hip), bit for bit."""
+    return torch.tensor(C().drop_path_mask(int(seed) & ((1 << 64) - 1), int(draw) & ((1 << 64) - 1), int(n),
+                                           float(p_drop)), dtype=torch.float32)
+
+
+def drop_path_scale(x, mask):
+    """y[n] = mask[n] * x[n] (mask float32 [N]); a dropped sample is not read."""
+    x = _c(x)
+    if mask.dtype != torch.float32 or mask.numel() != x.shape[0] or not mask.is_contiguous():
+        raise ValueError(f"drop_path_scale: x {tuple(x.shape)}, mask {tuple(mask.shape)} {mask.dtype}")
+    y = torch.empty_like(x)
+    C().drop_path_scale(dt(x), x.data_ptr(), mask.data_ptr(), y.data_ptr(), x.shape[0], x.numel() // max(x.shape[0], 1))
+    return y

@@ -212,6 +212,83 @@ def counter_bump(ctr, slot):
     kernels().counter_bump(ctr.data_ptr(), slot.data_ptr(), stream_ptr())
 
 
+def _dp_mask_ok(mask, n, what):
+    if mask.dtype != F32 or not mask.is_cuda or mask.numel() != n or not mask.is_contiguous():
+        raise ValueError(f"{what}: mask must be a contiguous fp32 GPU tensor of {n} values, got "
+                         f"{tuple(mask.shape)} {mask.dtype}")
+
+
+def drop_path_mask(mask, p, seed, draw=0, slot=None):
+    """Write the stochastic-depth mask (droppath.hip) of ``mask.numel()`` samples into ``mask``
+    (fp32): 0 with probability p, else 1 / (1 - p), from Philox(seed, draw). ``slot``: a 1-element
+    int64 device tensor written by :func:`counter_bump` that holds the draw index instead (graph
+    replays then draw a new mask each)."""
+    _dp_mask_ok(mask, mask.numel(), "drop_path_mask")
+    _rec("drop_path_mask", n=mask.numel())
+    kernels().drop_path_mask_into(mask.data_ptr(), mask.numel(), float(p), int(seed) & ((1 << 64) - 1),
+                                  int(draw) & ((1 << 64) - 1), ptr(slot), stream_ptr())
+    return mask
+
+
+def drop_path_scale(x, mask, residual=None):
+    """y[n] = mask[n] * x[n] (+ residual[n]): the standalone DropPath forward and backward
+    (droppath.hip). x: a dense bf16 / fp32 tensor whose samples are contiguous (channels_last 4-D
+    or contiguous), at any offset; a dropped sample is written without reading x."""
+    if x.dtype not in (F32, BF16) or not x.is_cuda or x.dim() < 1:
+        raise ValueError(f"drop_path_scale: expected a bf16 / fp32 GPU tensor, got {tuple(x.shape)} {x.dtype}")
+    if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=CL))):
+        raise ValueError(f"drop_path_scale: x {tuple(x.shape)} strides {tuple(x.stride())} is not dense per sample")
+    N = x.shape[0]
+    _dp_mask_ok(mask, N, "drop_path_scale")
+    if residual is not None and (tuple(residual.shape) != tuple(x.shape) or residual.dtype != x.dtype or not (
+            residual.is_contiguous() if x.is_contiguous() else residual.is_contiguous(memory_format=CL))):
+        raise ValueError("drop_path_scale: the residual must match x in shape, dtype and layout")
+    _rec("drop_path_scale", x=tuple(x.shape), residual=residual is not None)
+    # the kernel's 16-byte vectors need x, the residual and the (16-byte aligned) output at the same
+    # address modulo 16: a dense view at another offset (batch[k:] of odd rows) is copied first
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.preserve_format)
+    if residual is not None and residual.data_ptr() % 16:
+        residual = residual.clone(memory_format=torch.preserve_format)
+    y = _empty_like(x)
+    kernels().drop_path_scale(dt_code(x.dtype), x.data_ptr(), mask.data_ptr(), ptr(residual), y.data_ptr(), N,
+                              x.numel() // N, stream_ptr())
+    return y
+
+
+def lscale_drop_fwd(x, gamma, mask, residual):
+    """The scale tail with stochastic depth (lnorm.hip): y = residual + mask[n] * gamma[c] * x in
+    one store; a dropped sample copies its residual rows without reading x."""
+    R, C = ln_rows(x, "lscale_drop_fwd")
+    assert gamma.dtype == F32 and gamma.numel() == C and gamma.is_contiguous(), "lscale_drop_fwd: gamma fp32 [C]"
+    _ln_like(residual, x, "lscale_drop_fwd.residual")
+    N = x.shape[0]
+    _dp_mask_ok(mask, N, "lscale_drop_fwd")
+    _rec("lscale_drop_fwd", x=tuple(x.shape))
+    y = _empty_like(x)
+    kernels().lscale_drop_fwd(dt_code(x.dtype), x.data_ptr(), gamma.data_ptr(), mask.data_ptr(), residual.data_ptr(),
+                              y.data_ptr(), R, C, R // N, stream_ptr())
+    return y
+
+
+def lscale_drop_bwd(dy, x, gamma, mask, dgamma):
+    """dx = mask[n] * gamma[c] * dy; dgamma += sum mask[n] * dy * x through the LayerScale's slab
+    and fixed-order reduce (bit-reproducible); a dropped sample gets zeros without reading x."""
+    R, C = ln_rows(x, "lscale_drop_bwd")
+    _ln_like(dy, x, "lscale_drop_bwd.dy")
+    for t in (gamma, dgamma):
+        assert t.dtype == F32 and t.numel() == C and t.is_contiguous(), "lscale_drop_bwd: gamma / dgamma fp32 [C]"
+    N = x.shape[0]
+    _dp_mask_ok(mask, N, "lscale_drop_bwd")
+    _rec("lscale_drop_bwd", x=tuple(x.shape))
+    K = kernels()
+    dx = _empty_like(x)
+    ws = _empty((K.ln_partial_rows(R, C), C), F32, x.device)
+    K.lscale_drop_bwd(dt_code(x.dtype), dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mask.data_ptr(), dx.data_ptr(),
+                      dgamma.data_ptr(), R, C, R // N, ws.data_ptr(), stream_ptr())
+    return dx
+
+
 # ------------------------------------------------------------------------------ loss / optim
 LOSS_CODES = {"crossentropy": 0, "softmax_crossentropy": 1, "logsoftmax_crossentropy": 2, "mse": 3, "mae": 4,
               "huber": 5}
@@ -239,7 +316,17 @@ def loss_fused(pred2d, target2d=None, labels=None, kind="softmax_crossentropy", 
     return loss, grad, correct
 
 
-def adam_step(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, wd, decoupled, hyper=None):
+def adam_step(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, wd, decoupled, hyper=None, nodecay=None):
+    """One Adam / AdamW step over a flat buffer. ``nodecay`` (uint8 device tensor, one byte per
+    64-element block): flagged blocks step with wd = 0 (its own kernel instance; without it the
+    launch is the plain adam_kernel)."""
+    if nodecay is not None:
+        if nodecay.dtype != torch.uint8 or not nodecay.is_cuda or nodecay.numel() * 64 < p.numel():
+            raise ValueError("adam_step: nodecay is a uint8 GPU tensor with one entry per 64 elements")
+        kernels().adam_step_nodecay(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(shadow), p.numel(),
+                                    float(lr), float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd),
+                                    int(decoupled), ptr(hyper), nodecay.data_ptr(), stream_ptr())
+        return
     kernels().adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(shadow), p.numel(), float(lr),
                         float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled),
                         ptr(hyper), stream_ptr())

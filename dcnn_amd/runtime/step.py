@@ -105,6 +105,12 @@ class TrainStep:
             ts += list(getattr(self.opt, name, None) or [])
         for l in self.model.layers:
             ts += _bn_buffers(l)
+        from ..nn.sequential import _all_layers
+        for l in _all_layers(self.model.layers):
+            # e.g. a DropPath's device draw counter, so replay k draws what eager step k draws.
+            # (Dropout keeps its behaviour from before DropPath existed: its counter is not rolled
+            # back, its masks after a capture start two draws later than in an eager run.)
+            ts += l.step_state()
         return ts
 
     def _capture_stream(self):

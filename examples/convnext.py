@@ -19,13 +19,17 @@ STATS = {"cifar10": ((0.49139968, 0.48215827, 0.44653124), (0.24703233, 0.243485
 def _args(ap):
     ap.add_argument("--tiny", action="store_true", help="ConvNeXt-T on Tiny-ImageNet-200 (64x64, 200 classes)")
     ap.add_argument("--steps", type=int, default=0, help="smoke mode: this many steps on synthetic data")
+    ap.add_argument("--drop-path", type=float, default=0.0,
+                    help="stochastic depth: the rate of the last block, rising linearly from 0 (ConvNeXt-T: 0.1)")
+    ap.add_argument("--no-decay-norm-bias", action="store_true",
+                    help="keep biases, norm affines and layer scales out of AdamW's weight decay")
 
 
 a, cfg = parse(__doc__, _args)
 kind = "tiny" if a.tiny else "cifar10"
 name = "convnext_tiny_tiny_imagenet" if a.tiny else "convnext_pico_cifar10"
-model = place(create_model(name), a)
-opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05)
+model = place(create_model(name, drop_path_rate=a.drop_path), a)
+opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05, no_decay_norm_bias=a.no_decay_norm_bias)
 loss_fn = LossFactory.create("softmax_crossentropy")
 if a.steps > 0:
     opt.attach(model)

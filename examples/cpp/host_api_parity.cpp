@@ -16,8 +16,9 @@
 //   host_api_parity resblock <in> <out> <hw> <batch> <out.bin> [--device GPU]
 //                                              one stride-2 basic residual block, forward + backward on
 //                                              fixed data; its input gradient and parameter gradients
-//   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph]
+//   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph] [--adamw-no-decay]
 //                                              Adam steps on a synthetic set, then save
+//   grads / train also take [--drop-path RATE] [--seed-drop-path] (ConvNeXt models)
 // Output is plain text: one "key v0 v1 ..." line per item.
 #include <algorithm>
 #include <cmath>
@@ -31,6 +32,39 @@
 #include "dcnn/train.hpp"
 
 using namespace dcnn;
+
+// --drop-path RATE: the ConvNeXt models' stochastic depth; --seed-drop-path: block k's DropPath gets
+// the explicit seed 1000 + k (a checkpoint then draws the same masks in the Python front end)
+static float drop_path_arg(int argc, char** argv) {
+  for (int i = 1; i + 1 < argc; ++i)
+    if (std::string(argv[i]) == "--drop-path") return (float)std::atof(argv[i + 1]);
+  return 0.f;
+}
+static bool flag_arg(int argc, char** argv, const char* f) {
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == f) return true;
+  return false;
+}
+// "convnext_two_block" (not a zoo model): 3x16x16 input, 2x2 / stride-2 stem to 16 channels, two
+// ConvNeXt blocks (layer scale 0.5) with DropPath at rate 0.5 and explicit seeds, pool, LayerNorm, fc
+static const char* kTwoBlock = "convnext_two_block";
+static int input_hw(const std::string& name) {
+  return name == kTwoBlock ? 16 : name.find("cifar") != std::string::npos ? 32 : 64;
+}
+static int num_classes(const std::string& name) {
+  return name == kTwoBlock || name.find("cifar") != std::string::npos ? 10 : 200;
+}
+static Sequential model_arg(int argc, char** argv, const std::string& name) {
+  if (name == kTwoBlock) {
+    SequentialBuilder b("cnx_dp");
+    b.input({3, 16, 16}).conv2d(16, 2, 2, 2, 2, 0, 0, true, "stem_conv").layernorm(1e-6f, true, "stem_ln")
+        .convnext_block(16, 0.5f, "block1", 0.5f, true, 101)
+        .convnext_block(16, 0.5f, "block2", 0.5f, true, (1ull << 40) + 7);
+    return b.avgpool2d(8, 8, 1, 1, 0, 0, "avgpool").layernorm(1e-6f, true, "head_ln").flatten("flatten")
+        .dense(10, true, "fc").build();
+  }
+  return create_model(name, drop_path_arg(argc, argv), flag_arg(argc, argv, "--seed-drop-path") ? 1000 : 0);
+}
 
 static Device device_arg(int argc, char** argv) {
   for (int i = 1; i + 1 < argc; ++i)
@@ -109,12 +143,11 @@ int main(int argc, char** argv) {
       // one forward + backward on the first synthetic batch; every parameter's gradient is
       // written (logical NCHW fp32 records, parameter order) to argv[4]
       const Device dev = device_arg(argc, argv);
-      Sequential m = create_model(argv[2]);
+      Sequential m = model_arg(argc, argv, argv[2]);
       m.set_device(dev);
       m.initialize(11);
       const int batch = std::atoi(argv[3]);
-      const bool cifar = std::string(argv[2]).find("cifar") != std::string::npos;
-      const int hw = cifar ? 32 : 64, classes = cifar ? 10 : 200;
+      const int hw = input_hw(argv[2]), classes = num_classes(argv[2]);
       SyntheticClassification data((size_t)batch, 3, hw, hw, classes, 5, 0.3f);
       Loss loss = LossFactory::create("softmax_crossentropy");
       data.reset(0);
@@ -307,14 +340,16 @@ int main(int argc, char** argv) {
     }
     if (cmd == "train" && argc >= 6) {
       const Device dev = device_arg(argc, argv);
-      Sequential m = create_model(argv[2]);
+      Sequential m = model_arg(argc, argv, argv[2]);
       m.set_device(dev);
       m.initialize(11);
       const int steps = std::atoi(argv[3]), batch = std::atoi(argv[4]);
-      const bool cifar = std::string(argv[2]).find("cifar") != std::string::npos;
-      const int hw = cifar ? 32 : 64, classes = cifar ? 10 : 200;
+      const int hw = input_hw(argv[2]), classes = num_classes(argv[2]);
       SyntheticClassification data((size_t)batch * steps, 3, hw, hw, classes, 5, 0.3f);
-      Adam opt(1e-3f);
+      // --adamw-no-decay: AdamW, weight decay 0.1, biases / norm affines / layer scales excluded
+      const bool nd = flag_arg(argc, argv, "--adamw-no-decay");
+      Adam opt(1e-3f, 0.9f, 0.999f, 1e-8f, nd ? 0.1f : 0.f, nd);
+      opt.set_no_decay_norm_bias(nd);
       Loss loss = LossFactory::create("softmax_crossentropy");
       data.reset(0);
       Tensor x, y;
