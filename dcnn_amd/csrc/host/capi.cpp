@@ -246,6 +246,57 @@ int dcnn_c_drop_path_mask_host(float* mask, long N, float p, uint64_t seed, uint
   return -1;
 }
 
+// Mixup / CutMix. The plan of training batch `step`: out6 = {mode, yl, yh, xl, xh, 0}, *lam = lam.
+int dcnn_c_mix_plan(uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha, double prob,
+                    double switch_prob, int* out6, double* lam) {
+  try {
+    const MixPlan p = cpu_ops::mix_plan(seed, step, H, W, mixup_alpha, cutmix_alpha, prob, switch_prob);
+    out6[0] = p.mode; out6[1] = p.yl; out6[2] = p.yh; out6[3] = p.xl; out6[4] = p.xh; out6[5] = 0;
+    *lam = p.lam;
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+// x fp32 [B][C][H][W] (device) mixed in place, target fp32 [B][K]; box = {yl, yh, xl, xh}
+int dcnn_c_mix_batch(float* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode,
+                     double lam, const int* box, long K) {
+  return guarded([&] { gpu_ops::mix_batch(x, labels, target, B, C, H, W, mode, lam, box[0], box[1], box[2], box[3], K); });
+}
+
+// the same on the CPU backend, host pointers
+int dcnn_c_mix_batch_host(float* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode,
+                          double lam, const int* box, long K) {
+  try {
+    cpu_ops::mix_batch(x, labels, target, B, C, H, W, mode, lam, box[0], box[1], box[2], box[3], K);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+// Soft-target cross entropy with label smoothing eps. Device: pred / grad bf16 [N][C], target fp32
+// [N][C] or null with int64 labels; *loss the mean loss, *correct the argmax hits.
+int dcnn_c_soft_loss(const void* pred, const float* target, const int64_t* labels, void* grad, int N, int C, float eps,
+                     float grad_scale, double* loss, long* correct) {
+  return guarded([&] { *loss = gpu_ops::loss(6, pred, target, labels, grad, N, C, eps, correct, grad_scale); });
+}
+
+// the same on the CPU backend: pred / grad fp32 host pointers
+int dcnn_c_soft_loss_host(const float* pred, const float* target, const int64_t* labels, float* grad, long N, long C,
+                          float eps, double* loss, long* correct) {
+  try {
+    *loss = cpu_ops::loss(6, pred, target, labels, grad, N, C, eps, correct);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
 // y[n][:] = mask[n] x[n][:] (+ residual[n][:]), bf16, samples of `row` elements
 int dcnn_c_drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row) {
   return guarded([&] { gpu_ops::drop_path_scale(x, mask, residual, y, N, row); });

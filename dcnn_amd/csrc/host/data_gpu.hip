@@ -123,6 +123,11 @@ bool DeviceImageDataset::next(int batch, Tensor& x, Tensor& labels) {
   }
   augment_batch(a, static_cast<hipStream_t>(gpu::flow()));
   pos_ += (size_t)b;
+  if (mixer_) {
+    Tensor target;
+    mixer_->mix(x, labels, target);
+    labels = target;
+  }
   return true;
 }
 

@@ -18,6 +18,13 @@ enum ActKind {
   ACT_GELU = 6  // exact: x Phi(x)
 };
 
+// one batch's Mixup / CutMix draw: mode 0 none, 1 Mixup, 2 CutMix with the box [yl, yh) x [xl, xh)
+struct MixPlan {
+  int mode;
+  double lam;
+  int yl, yh, xl, xh;
+};
+
 namespace cpu_ops {
 void conv_fwd(const float* x, const float* w, const float* b, float* y, const ConvShape& s);
 void conv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, const ConvShape& s);
@@ -42,8 +49,8 @@ void avgpool_bwd(const float* dy, float* dx, const PoolShape& p);
 void act_fwd(int kind, const float* x, float* y, long n, float alpha);
 void act_bwd(int kind, const float* x, const float* dy, float* dx, long n, float alpha);
 double softmax_ce(const float* pred, const int64_t* labels, float* grad, long N, long C, long* correct);
-// the six losses (kind: 0 ce, 1 softmax ce, 2 log-softmax ce, 3 mse, 4 mae, 5 huber); target
-// [N][C] fp32 or null (then `labels` are one-hot targets)
+// the losses (kind: 0 ce, 1 softmax ce, 2 log-softmax ce, 3 mse, 4 mae, 5 huber, 6 soft-target ce
+// with param = label smoothing); target [N][C] fp32 or null (then `labels` are one-hot targets)
 double loss(int kind, const float* pred, const float* target, const int64_t* labels, float* grad, long N, long C,
             float param, long* correct);
 void groupnorm_fwd(const float* x, float* y, long N, long C, long HW, long G, const float* g, const float* b, float eps,
@@ -78,6 +85,14 @@ void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr
 // library and the native backend; y[n][:] = mask[n] x[n][:] over samples of `row` elements
 void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw);
 void drop_path_scale(const float* x, const float* mask, float* y, long N, long row);
+// Mixup / CutMix. mix_plan: the draw of training batch `step` (from 1), a pure host function of its
+// arguments - the native module's, so both front ends plan the same batches. mix_batch: x fp32
+// [B][C][H][W] mixed in place with the reversed batch, target fp32 [B][K] written whole (host
+// pointers; the bits of gpu_ops::mix_batch). Bad arguments throw std::invalid_argument.
+MixPlan mix_plan(uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha, double prob,
+                 double switch_prob);
+void mix_batch(float* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K);
 }  // namespace cpu_ops
 
 namespace gpu_ops {
@@ -323,6 +338,10 @@ void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow
 void drop_path_draw(float* mask, int N, float p, uint64_t seed, uint64_t* ctr, uint64_t* slot);
 void drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw);
 void drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row);
+// Mixup / CutMix of a device batch (mix.hip): x fp32 [B][C][H][W] in place, target fp32 [B][K], one
+// launch on the flow
+void mix_batch(float* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K);
 void layer_scale_drop_fwd(const void* x, const float* g, const float* mask, const void* residual, void* y, long R,
                           int C, long rps);
 void layer_scale_drop_bwd(const void* dy, const void* x, const float* g, const float* mask, void* dx, float* dg,

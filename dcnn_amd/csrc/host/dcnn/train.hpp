@@ -24,7 +24,8 @@ namespace dcnn {
 // Mean over the batch; targets are class labels (one-hot) or, for the regression losses, an
 // optional dense [N, C] fp32 target. kind codes match the fused kernels: 0 crossentropy (on
 // probabilities, eps-clamped), 1 softmax crossentropy, 2 log-softmax crossentropy, 3 mse, 4 mae,
-// 5 huber(delta).
+// 5 huber(delta), 6 soft-target crossentropy (param = label smoothing; a dense target of any rows,
+// e.g. a BatchMixer's, or labels).
 class Loss {
  public:
   Loss(int kind, float param, std::string type) : kind_(kind), param_(param), type_(std::move(type)) {}
@@ -32,7 +33,10 @@ class Loss {
   // grad_scale multiplies the gradient (e.g. 1 / micro-batches), not the loss value
   LossResult compute(const Tensor& pred, const Tensor* labels, const Tensor* target = nullptr,
                      float grad_scale = 1.f) const;
-  LossResult operator()(const Tensor& pred, const Tensor& labels) const { return compute(pred, &labels); }
+  // y: int64 labels [N], or an fp32 target [N, C]
+  LossResult operator()(const Tensor& pred, const Tensor& y) const {
+    return y.dtype() == DType::F32 ? compute(pred, nullptr, &y) : compute(pred, &y);
+  }
   const std::string& type() const { return type_; }
   int kind() const { return kind_; }
   float param() const { return param_; }
@@ -52,7 +56,9 @@ class Loss {
 class TrainGraph {
  public:
   TrainGraph(Sequential& model, Adam& opt, const Loss& loss) : model_(model), opt_(opt), loss_(loss) {}
-  double step(const Tensor& x, const Tensor& labels);  // eager on the first call: captures, then replays
+  // eager on the first call: captures, then replays. y: int64 labels [N] or an fp32 target [N, C];
+  // the static slot takes the first batch's dtype and shape, another one later throws
+  double step(const Tensor& x, const Tensor& y);
   double last_loss();                                  // host read of the last replay's loss
   // runs between the backward and the optimizer of every step, inside the capture (e.g. the
   // data-parallel gradient all-reduce, dist::DataParallel::all_reduce_mean on the arena gradient)
@@ -71,8 +77,29 @@ class TrainGraph {
 
 struct LossFactory {
   // "crossentropy"|"ce", "softmax_crossentropy"|"softmax_ce", "logsoftmax_crossentropy"|
-  // "logsoftmax_ce", "mse", "mae", "huber" (param: delta)
+  // "logsoftmax_ce", "mse", "mae", "huber" (param: delta), "soft_crossentropy"|"soft_ce"|
+  // "label_smoothing_ce" (param: label smoothing in [0, 1), default 0)
   static Loss create(const std::string& name, float param = -1.f);
+};
+
+// Mixup / CutMix of a training batch (the Python front end's data/mix.py BatchMixer: the same
+// parameters, the same counter, the same draws - cpu_ops::mix_plan). mix(): x fp32 [B, C, H, W] on
+// either device is mixed in place with its reversed batch, target becomes the dense fp32 [B, K]
+// target on x's device, and the step counter advances. Train against it with "soft_crossentropy".
+class BatchMixer {
+ public:
+  BatchMixer(int num_classes, double mixup_alpha = 0.8, double cutmix_alpha = 1.0, double prob = 1.0,
+             double switch_prob = 0.5, uint64_t seed = 0);
+  MixPlan plan(uint64_t step, int H, int W) const;
+  void mix(Tensor& x, const Tensor& labels, Tensor& target);
+  uint64_t state() const { return state_; }
+  void set_state(uint64_t s) { state_ = s; }
+  int num_classes() const { return k_; }
+
+ private:
+  int k_;
+  double ma_, ca_, prob_, sw_;
+  uint64_t seed_, state_ = 0;
 };
 
 // ---------------------------------------------------------------- schedulers
@@ -302,8 +329,11 @@ class DeviceImageDataset : public DataSource {
   DeviceImageDataset& normalize(const std::vector<float>& mean = {0.485f, 0.456f, 0.406f},
                                 const std::vector<float>& stdev = {0.229f, 0.224f, 0.225f});
   void reset(uint64_t epoch) override;
-  // x: fp32 [B, C, H, W] and labels int64 [B], both on the device
+  // x: fp32 [B, C, H, W] and labels int64 [B], both on the device; with a mixer (set_mixer, not
+  // owned, nullptr switches it off) the batch is mixed behind the augmentation on the same flow and
+  // `labels` receives the dense fp32 [B, K] target instead
   bool next(int batch, Tensor& x, Tensor& labels) override;
+  void set_mixer(BatchMixer* m) { mixer_ = m; }
   size_t size() const override { return n_; }
   bool stored_u8() const { return u8_; }
   size_t device_bytes() const { return data_.nbytes(); }
@@ -324,6 +354,7 @@ class DeviceImageDataset : public DataSource {
   int c_, h_, w_;
   uint64_t seed_, epoch_ = 0;
   bool shuffle_, drop_last_, u8_ = false;
+  BatchMixer* mixer_ = nullptr;
 };
 
 // MNIST CSV (label, 784 pixels per row; header row auto-detected) -> [N, 1, 28, 28] / 255

@@ -88,9 +88,10 @@ double softmax_ce(const float* pred, const int64_t* labels, float* grad, long N,
 
 double loss(int kind, const float* pred, const float* target, const int64_t* labels, float* grad, long N, long Cc,
             float param, long* correct) {
-  // the CPU kernels number the losses 0 ce, 1 softmax ce (= log-softmax ce), 2 mse, 3 mae, 4 huber
-  static const int map[] = {0, 1, 1, 2, 3, 4};
-  if (kind < 0 || kind > 5) throw std::invalid_argument("loss: unknown kind");
+  // the CPU kernels number the losses 0 ce, 1 softmax ce (= log-softmax ce), 2 mse, 3 mae, 4 huber,
+  // 5 soft-target ce
+  static const int map[] = {0, 1, 1, 2, 3, 4, 5};
+  if (kind < 0 || kind > 6) throw std::invalid_argument("loss: unknown kind");
   return C::loss_fused(map[kind], pred, target, labels, grad, N, Cc, param, correct);
 }
 
@@ -163,6 +164,17 @@ void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr
 
 void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw) {
   C::drop_path_mask(mask, N, p, seed, draw);
+}
+
+MixPlan mix_plan(uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha, double prob,
+                 double switch_prob) {
+  const C::MixPlan p = C::mix_plan(seed, step, H, W, mixup_alpha, cutmix_alpha, prob, switch_prob);
+  return MixPlan{p.mode, p.lam, p.yl, p.yh, p.xl, p.xh};
+}
+
+void mix_batch(float* x, const int64_t* labels, float* target, long B, long Cc, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K) {
+  C::mix_batch<float>(x, labels, target, B, Cc, H, W, mode, lam, yl, yh, xl, xh, K);
 }
 
 void drop_path_scale(const float* x, const float* mask, float* y, long N, long row) {

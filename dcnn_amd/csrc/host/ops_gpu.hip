@@ -1190,6 +1190,15 @@ void drop_path_draw(float* mask, int N, float p, uint64_t seed, uint64_t* ctr, u
 void drop_path_mask(float* mask, int N, float p, uint64_t seed, uint64_t draw) {
   dcnn::drop_path_mask(mask, N, p, seed, draw, nullptr, cur());
 }
+void mix_batch(float* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K) {
+  if (B < 1 || C < 1 || H < 1 || W < 1 || (double)B * C * H * W > 2147483647.0)
+    throw std::invalid_argument("mix_batch: " + std::to_string((double)B * C * H * W) +
+                                " elements: the batch is empty or exceeds 2^31 - 1");
+  if (K < 1 || (double)B * K > 2147483647.0)
+    throw std::invalid_argument("mix_batch: num_classes " + std::to_string(K) + " < 1 or the target exceeds 2^31 - 1");
+  dcnn::mix_batch(x, labels, target, (int)B, (int)C, (int)H, (int)W, mode, (float)lam, yl, yh, xl, xh, (int)K, cur());
+}
 void drop_path_scale(const void* x, const float* mask, const void* residual, void* y, long N, long row) {
   dcnn::drop_path_scale(kBF16, x, mask, residual, y, N, row, cur());
 }

@@ -114,8 +114,11 @@ double TrainGraph::step(const Tensor& x, const Tensor& labels) {
     return r.loss;
   }
   if (!captured_) capture(x, labels);
-  if (x.numel() != sx_.numel() || labels.numel() != sy_.numel())
-    throw std::runtime_error("TrainGraph: the batch shape changed after capture");
+  if (x.numel() != sx_.numel() || labels.numel() != sy_.numel() || labels.dtype() != sy_.dtype())
+    throw std::runtime_error("TrainGraph: the batch shape changed after capture (the target slot is " +
+                             std::string(dtype_name(sy_.dtype())) + " with " + std::to_string(sy_.numel()) +
+                             " elements, got " + dtype_name(labels.dtype()) + " with " +
+                             std::to_string(labels.numel()) + ")");
   // the batch into the static slots (device-resident batches: stream-ordered D2D copies, both in
   // one kernel launch)
   if (x.device() == dev && labels.device() == dev) {
@@ -150,7 +153,41 @@ Loss LossFactory::create(const std::string& name, float param) {
   if (n == "mse") return Loss(3, 0.f, "mse");
   if (n == "mae") return Loss(4, 0.f, "mae");
   if (n == "huber") return Loss(5, param >= 0 ? param : 1.0f, "huber");
+  if (n == "soft_crossentropy" || n == "soft_ce" || n == "label_smoothing_ce") {
+    const float eps = param >= 0 ? param : 0.f;
+    if (!(eps < 1.f)) throw std::invalid_argument("label_smoothing must be in [0, 1), got " + std::to_string(eps));
+    return Loss(6, eps, "soft_crossentropy");
+  }
   throw std::invalid_argument("unknown loss '" + name + "'");
+}
+
+// ================================================================= Mixup / CutMix
+BatchMixer::BatchMixer(int num_classes, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob,
+                       uint64_t seed)
+    : k_(num_classes), ma_(mixup_alpha), ca_(cutmix_alpha), prob_(prob), sw_(switch_prob), seed_(seed) {
+  if (k_ < 1) throw std::invalid_argument("BatchMixer: num_classes " + std::to_string(k_) + " < 1");
+  plan(1, 1, 1);  // the argument checks of mix_plan
+}
+
+MixPlan BatchMixer::plan(uint64_t step, int H, int W) const {
+  return cpu_ops::mix_plan(seed_, step, H, W, ma_, ca_, prob_, sw_);
+}
+
+void BatchMixer::mix(Tensor& x, const Tensor& labels_in, Tensor& target) {
+  if (x.rank() != 4 || x.dtype() != DType::F32) throw std::invalid_argument("BatchMixer: x is fp32 [B, C, H, W]");
+  if (labels_in.dtype() != DType::I64 || labels_in.numel() != x.dim(0))
+    throw std::invalid_argument("BatchMixer: labels are int64 [B]");
+  const Device dev = x.device();
+  const long B = x.dim(0), C = x.dim(1), H = x.dim(2), W = x.dim(3);
+  const Tensor labels = labels_in.device() == dev ? labels_in : labels_in.to(dev);
+  const MixPlan p = plan(++state_, (int)H, (int)W);
+  target = Tensor::empty({B, (int64_t)k_}, DType::F32, dev);
+  if (dev.is_gpu())
+    gpu_ops::mix_batch(x.ptr<float>(), labels.ptr<int64_t>(), target.ptr<float>(), B, C, H, W, p.mode, p.lam, p.yl,
+                       p.yh, p.xl, p.xh, k_);
+  else
+    cpu_ops::mix_batch(x.ptr<float>(), labels.ptr<int64_t>(), target.ptr<float>(), B, C, H, W, p.mode, p.lam, p.yl,
+                       p.yh, p.xl, p.xh, k_);
 }
 
 // ================================================================= schedulers

@@ -368,6 +368,14 @@ void im2col(const float* x, float* col, int N, int C, int H, int W, int KH, int 
             int OH, int OW, hipStream_t s);
 void col2im(const float* col, float* x, int N, int C, int H, int W, int KH, int KW, int SH, int SW, int PH, int PW,
             int OH, int OW, hipStream_t s);
+// Mixup / CutMix (mix.hip): x fp32 [B, C, H, W] mixed in place with the reversed batch (partner of
+// i is B - 1 - i), target fp32 [B, K] written whole, one launch. mode 0 none, 1 Mixup
+// (fma(lam, x_i, (1 - lam) x_j)), 2 CutMix (the box [yl, yh) x [xl, xh) swapped). Bad arguments
+// throw std::invalid_argument naming the value.
+void mix_batch(float* x, const int64_t* labels, float* target, int B, int C, int H, int W, int mode, float lam, int yl,
+               int yh, int xl, int xh, int K, hipStream_t s);
+// loss kinds: 0 ce, 1 softmax ce, 2 log-softmax ce, 3 mse, 4 mae, 5 huber, 6 soft-target ce (param =
+// label smoothing)
 int loss_workspace_floats(int N);
 void loss_fused(int dt, const void* pred, const float* target, const int64_t* labels, void* grad, float* loss_out,
                 int* correct, int N, int C, int type, float param, float gscale, float* ws, unsigned* ticket,

@@ -680,6 +680,17 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("grad_unpack_bf16", [](uintptr_t in, uintptr_t g, long n, uintptr_t st) {
     grad_unpack_bf16(P<const bf16*>(in), P<float*>(g), n, S(st));
   });
+  // Mixup / CutMix of a device batch in place + its dense target (mix.hip)
+  m.def("mix_batch", [](uintptr_t x, uintptr_t labels, uintptr_t target, long B, long C, long H, long W, int mode,
+                        double lam, int yl, int yh, int xl, int xh, long K, uintptr_t st) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || (double)B * C * H * W > 2147483647.0)
+      throw std::invalid_argument("mix_batch: " + std::to_string((double)B * C * H * W) +
+                                  " elements: the batch is empty or exceeds 2^31 - 1");
+    if (K < 1 || (double)B * K > 2147483647.0)
+      throw std::invalid_argument("mix_batch: num_classes " + std::to_string(K) + " < 1 or the target exceeds 2^31 - 1");
+    mix_batch(P<float*>(x), P<const int64_t*>(labels), P<float*>(target), (int)B, (int)C, (int)H, (int)W, mode,
+              (float)lam, yl, yh, xl, xh, (int)K, S(st));
+  });
   m.def("augment_batch_supported", &augment_batch_supported);
   // ops: (kind, probability, params[<= 6]) in chain order
   m.def("augment_batch", [](uintptr_t src, int src_u8, uintptr_t idx, uintptr_t labels, uintptr_t labels_out,

@@ -13,7 +13,7 @@
 
 namespace dcnn {
 
-enum LossType { kCE = 0, kSoftmaxCE = 1, kLogSoftmaxCE = 2, kMSE = 3, kMAE = 4, kHuber = 5 };
+enum LossType { kCE = 0, kSoftmaxCE = 1, kLogSoftmaxCE = 2, kMSE = 3, kMAE = 4, kHuber = 5, kSoftCE = 6 };
 
 // One wave per sample row (4 rows per workgroup). Each row's loss and hit are written to a
 // workspace; the workgroups then take a ticket and the last one sums the N row values in a
@@ -64,6 +64,31 @@ __device__ __forceinline__ void loss_row(const T* __restrict__ pred, const float
       const float inv_s = 1.f / s;
       for (int c = lane; c < C; c += 64)
         grad[(long)row * C + c] = from_f<T>((__expf(to_f(p[c]) - pm) * inv_s - tgt(c)) * ginvN);
+    }
+  } else if (type == kSoftCE) {
+    // soft-target CE with label smoothing (param = eps): t' = (1 - eps) t + eps / C, S = sum t',
+    // loss = S lse - sum t' x, grad = S softmax - t'. No hot class: any dense target is valid.
+    const float keep = 1.f - param, fl = param / (float)C;
+    float s = 0.f, S = 0.f, dot = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float v = to_f(p[c]), ts = __fmaf_rn(keep, tgt(c), fl);
+      s += __expf(v - pm);
+      S += ts;
+      dot = __fmaf_rn(ts, v, dot);
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // S and sum t' x in one pass over the wave
+      S += __shfl_xor(S, o, 64);
+      dot += __shfl_xor(dot, o, 64);
+    }
+    const float lse = pm + __logf(s);
+    lsum = (S * lse - dot) * invN;
+    if (grad) {
+      const float Sinv_s = S / s;
+      for (int c = lane; c < C; c += 64)
+        grad[(long)row * C + c] =
+            from_f<T>((__expf(to_f(p[c]) - pm) * Sinv_s - __fmaf_rn(keep, tgt(c), fl)) * ginvN);
     }
   } else if (type == kCE) {
     int hot = 0x7fffffff;
@@ -162,6 +187,9 @@ void loss_fused(int dt, const void* pred, const float* target, const int64_t* la
                 hipStream_t s) {
   const int blocks = (N + 3) / 4;
   if (blocks > 1 && (!ws || !ticket)) throw std::runtime_error("loss_fused: workspace required");
+  if (type < 0 || type > kSoftCE) throw std::invalid_argument("loss_fused: unknown loss kind " + std::to_string(type));
+  if (type == kSoftCE && !(param >= 0.f && param < 1.f))
+    throw std::invalid_argument("loss_fused: label_smoothing " + std::to_string(param) + " is not in [0, 1)");
   if (dt == 0)
     hipLaunchKernelGGL(loss_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)pred, target, labels,
                        (float*)grad, loss_out, correct, N, C, type, param, gscale, ws, ticket);

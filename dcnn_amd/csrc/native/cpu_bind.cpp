@@ -220,4 +220,16 @@ void bind_cpu(py::module_& parent) {
   m.def("drop_path_scale", [](int dt, uintptr_t x, uintptr_t mask, uintptr_t y, long N, long row) {
     DT_DISPATCH(dt, drop_path_scale<T>(P<const T>(x), P<const float>(mask), P<T>(y), N, row));
   }, Rel());
+  // Mixup / CutMix: the per-batch plan (mode, lam, yl, yh, xl, xh) and the in-place batch mix
+  m.def("mix_plan", [](uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha,
+                       double prob, double switch_prob) {
+    const MixPlan pl = mix_plan(seed, step, H, W, mixup_alpha, cutmix_alpha, prob, switch_prob);
+    return py::make_tuple(pl.mode, pl.lam, pl.yl, pl.yh, pl.xl, pl.xh);
+  });
+  m.def("mix_check", &mix_check);
+  m.def("mix_batch", [](int dt, uintptr_t x, uintptr_t labels, uintptr_t target, long B, long C, long H, long W,
+                        int mode, double lam, int yl, int yh, int xl, int xh, long K) {
+    DT_DISPATCH(dt, mix_batch<T>(P<T>(x), P<const int64_t>(labels), P<float>(target), B, C, H, W, mode, lam, yl, yh,
+                                 xl, xh, K));
+  }, Rel());
 }

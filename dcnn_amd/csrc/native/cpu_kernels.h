@@ -105,5 +105,22 @@ void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b
 void drop_path_mask(float* mask, long N, double p, uint64_t seed, uint64_t draw);
 template <typename T> void drop_path_scale(const T* x, const float* mask, T* y, long N, long row);
 
+// Mixup / CutMix. mix_plan: the per-batch draw, a pure function of (seed, step) - the only place
+// either front end draws. mode 0 none, 1 Mixup, 2 CutMix with the box [yl, yh) x [xl, xh).
+// mix_batch: x [B, C, H, W] mixed in place with the reversed batch, target [B, K] fp32 written
+// whole; the GPU kernel's rounding (csrc/kernels/mix.hip), bit for bit. mix_check: the argument
+// checks both backends share (throws std::invalid_argument naming the value).
+struct MixPlan {
+  int mode;
+  double lam;
+  int yl, yh, xl, xh;
+};
+MixPlan mix_plan(uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha, double prob,
+                 double switch_prob);
+void mix_check(long B, long C, long H, long W, long K, int mode, double lam, int yl, int yh, int xl, int xh);
+template <typename T>
+void mix_batch(T* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K);
+
 }  // namespace cpu
 }  // namespace dcnn_native

@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "cpu_kernels.h"
@@ -1034,6 +1035,152 @@ void drop_path_scale(const T* x, const float* mask, T* y, long N, long row) {
   });
 }
 
+// ------------------------------------------------------------------ Mixup / CutMix
+namespace {
+inline uint64_t aug_mix(uint64_t z) {  // splitmix64 finaliser (csrc/kernels/augment.hip aug_mix)
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// draw `d` of batch `step`: a double strictly inside (0, 1) with 52 bits, (k + 0.5) / 2^52
+inline double mix_u(uint64_t seed, uint64_t step, uint64_t d) {
+  const uint64_t h = aug_mix(seed ^ aug_mix(step * 0x100000001B3ull + (d << 40)));
+  return ((double)(h >> 12) + 0.5) * (1.0 / 4503599627370496.0);
+}
+// Gamma(a, 1) by Marsaglia & Tsang (2000): for a >= 1, d = a - 1/3, c = 1 / sqrt(9 d); draw a
+// normal x (Box-Muller, cosine branch, two uniforms) and a uniform u until v = (1 + c x)^3 > 0 and
+// log u < x^2 / 2 + d - d v + d log v; the value is d v. For a < 1 the boost: Gamma(a + 1) U^(1/a).
+// Every uniform is draw *d of the batch, and *d walks on: no state besides the index.
+double mix_gamma(double a, uint64_t seed, uint64_t step, uint64_t* d) {
+  const double boost = a < 1.0 ? std::pow(mix_u(seed, step, (*d)++), 1.0 / a) : 1.0;
+  const double aa = a < 1.0 ? a + 1.0 : a;
+  const double dd = aa - 1.0 / 3.0, c = 1.0 / std::sqrt(9.0 * dd);
+  for (;;) {
+    const double u1 = mix_u(seed, step, (*d)++), u2 = mix_u(seed, step, (*d)++), u = mix_u(seed, step, (*d)++);
+    const double x = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925 * u2);
+    const double t = 1.0 + c * x;
+    if (t <= 0.0) continue;
+    const double v = t * t * t;
+    if (std::log(u) < 0.5 * x * x + dd - dd * v + dd * std::log(v)) return dd * v * boost;
+  }
+}
+inline int clipi(long v, int lo, int hi) { return (int)std::min<long>(std::max<long>(v, lo), hi); }
+}  // namespace
+
+// The per-batch Mixup / CutMix draw (timm's Mixup in batch mode). Draw indices of (seed, step):
+// 0 apply (u < prob), 1 CutMix against Mixup (u < switch_prob, both alphas > 0), 2 / 3 the box
+// centre row / column, 16.. the two gammas of lam = Ga / (Ga + Gb) ~ Beta(alpha, alpha).
+MixPlan mix_plan(uint64_t seed, uint64_t step, int H, int W, double mixup_alpha, double cutmix_alpha, double prob,
+                 double switch_prob) {
+  if (!(mixup_alpha >= 0.0)) throw std::invalid_argument("mix_plan: mixup_alpha " + std::to_string(mixup_alpha) + " < 0");
+  if (!(cutmix_alpha >= 0.0))
+    throw std::invalid_argument("mix_plan: cutmix_alpha " + std::to_string(cutmix_alpha) + " < 0");
+  if (!(prob >= 0.0 && prob <= 1.0)) throw std::invalid_argument("mix_plan: prob " + std::to_string(prob) + " is not in [0, 1]");
+  if (!(switch_prob >= 0.0 && switch_prob <= 1.0))
+    throw std::invalid_argument("mix_plan: switch_prob " + std::to_string(switch_prob) + " is not in [0, 1]");
+  if (H < 1) throw std::invalid_argument("mix_plan: H " + std::to_string(H) + " < 1");
+  if (W < 1) throw std::invalid_argument("mix_plan: W " + std::to_string(W) + " < 1");
+  MixPlan pl{0, 1.0, 0, 0, 0, 0};
+  if ((mixup_alpha <= 0.0 && cutmix_alpha <= 0.0) || !(mix_u(seed, step, 0) < prob)) return pl;
+  bool cut = cutmix_alpha > 0.0;
+  if (cut && mixup_alpha > 0.0) cut = mix_u(seed, step, 1) < switch_prob;
+  const double alpha = cut ? cutmix_alpha : mixup_alpha;
+  uint64_t d = 16;
+  const double ga = mix_gamma(alpha, seed, step, &d), gb = mix_gamma(alpha, seed, step, &d);
+  double lam = ga + gb > 0.0 ? ga / (ga + gb) : 0.5;
+  lam = std::min(std::max(lam, 0.0), 1.0);
+  if (!cut) {
+    pl.mode = 1;
+    pl.lam = lam;
+    return pl;
+  }
+  const double r = std::sqrt(1.0 - lam);
+  const int ch = (int)(H * r), cw = (int)(W * r);
+  const int cy = std::min((int)(mix_u(seed, step, 2) * H), H - 1), cx = std::min((int)(mix_u(seed, step, 3) * W), W - 1);
+  pl.mode = 2;
+  pl.yl = clipi((long)cy - ch / 2, 0, H);
+  pl.yh = clipi((long)cy + ch / 2, 0, H);
+  pl.xl = clipi((long)cx - cw / 2, 0, W);
+  pl.xh = clipi((long)cx + cw / 2, 0, W);
+  const long area = (long)(pl.yh - pl.yl) * (pl.xh - pl.xl);
+  pl.lam = area > 0 ? 1.0 - (double)area / ((double)H * (double)W) : 1.0;
+  return pl;
+}
+
+void mix_check(long B, long C, long H, long W, long K, int mode, double lam, int yl, int yh, int xl, int xh) {
+  if (B < 1 || C < 1 || H < 1 || W < 1)
+    throw std::invalid_argument("mix_batch: empty batch " + std::to_string(B) + "x" + std::to_string(C) + "x" +
+                                std::to_string(H) + "x" + std::to_string(W));
+  if ((double)B * (double)C * (double)H * (double)W > 2147483647.0)
+    throw std::invalid_argument("mix_batch: " + std::to_string((double)B * C * H * W) + " elements exceed 2^31 - 1");
+  if (K < 1) throw std::invalid_argument("mix_batch: num_classes " + std::to_string(K) + " < 1");
+  if ((double)B * (double)K > 2147483647.0)
+    throw std::invalid_argument("mix_batch: " + std::to_string((double)B * K) + " target elements exceed 2^31 - 1");
+  if (mode < 0 || mode > 2) throw std::invalid_argument("mix_batch: mode " + std::to_string(mode) + " is not 0, 1 or 2");
+  if (!(lam >= 0.0 && lam <= 1.0)) throw std::invalid_argument("mix_batch: lam " + std::to_string(lam) + " is not in [0, 1]");
+  if (mode == 2 && !(0 <= yl && yl <= yh && yh <= H && 0 <= xl && xl <= xh && xh <= W))
+    throw std::invalid_argument("mix_batch: box [" + std::to_string(yl) + ", " + std::to_string(yh) + ") x [" +
+                                std::to_string(xl) + ", " + std::to_string(xh) + ") is outside the " +
+                                std::to_string(H) + "x" + std::to_string(W) + " image");
+}
+
+// Mixup / CutMix of a batch with its reverse, in place (partner of i is B - 1 - i), and the dense
+// fp32 target. The rounding is the GPU kernel's (csrc/kernels/mix.hip): 1 - lam and (1 - lam) x_j
+// each rounded to T, then one fused multiply-add, so both backends give the same bits.
+template <typename T>
+void mix_batch(T* x, const int64_t* labels, float* target, long B, long C, long H, long W, int mode, double lam,
+               int yl, int yh, int xl, int xh, long K) {
+  mix_check(B, C, H, W, K, mode, lam, yl, yh, xl, xh);
+  const float lamf = mode == 0 ? 1.0f : (float)lam;
+  const float omlf = 1.0f - lamf;
+  parallel_for(0, B, 16, [&](long lo, long hi) {
+    for (long i = lo; i < hi; ++i) {
+      float* t = target + i * K;
+      for (long k = 0; k < K; ++k) t[k] = 0.f;
+      const int64_t a = labels[i], b = labels[B - 1 - i];
+      if (a == b || mode == 0 || B - 1 - i == i) {
+        if (a >= 0 && a < K) t[a] = 1.0f;
+      } else {
+        if (a >= 0 && a < K) t[a] = lamf;
+        if (b >= 0 && b < K) t[b] = omlf;
+      }
+    }
+  });
+  const long row = C * H * W, pairs = B / 2;
+  if (mode == 1) {
+    const T l = (T)lam, o = (T)1 - l;
+    const long chunks = (row + kGrain - 1) / kGrain;
+    parallel_for(0, pairs * chunks, 1, [&](long lo, long hi) {
+      for (long w = lo; w < hi; ++w) {
+        const long pr = w / chunks, e0 = (w % chunks) * kGrain, e1 = std::min(row, e0 + kGrain);
+        T* xi = x + pr * row;
+        T* xj = x + (B - 1 - pr) * row;
+        for (long e = e0; e < e1; ++e) {
+          const T vi = xi[e], vj = xj[e];
+          const T pj = o * vj, pi = o * vi;
+          xi[e] = std::fma(l, vi, pj);
+          xj[e] = std::fma(l, vj, pi);
+        }
+      }
+    });
+  } else if (mode == 2 && yh > yl && xh > xl) {
+    parallel_for(0, pairs * C, 1, [&](long lo, long hi) {
+      for (long w = lo; w < hi; ++w) {
+        const long pr = w / C, c = w % C;
+        T* xi = x + pr * row + c * H * W;
+        T* xj = x + (B - 1 - pr) * row + c * H * W;
+        for (long yy = yl; yy < yh; ++yy)
+          for (long xx = xl; xx < xh; ++xx) std::swap(xi[yy * W + xx], xj[yy * W + xx]);
+      }
+    });
+  }
+}
+template void mix_batch<float>(float*, const int64_t*, float*, long, long, long, long, int, double, int, int, int, int,
+                               long);
+template void mix_batch<double>(double*, const int64_t*, float*, long, long, long, long, int, double, int, int, int,
+                                int, long);
+
 // ------------------------------------------------------------------ pooling
 // argmax index = iy * W + ix within the plane (first maximum in window order), -1 for an
 // all-padding window
@@ -1203,7 +1350,9 @@ void softmax_channels_bwd(const T* y, const T* dy, T* dx, long N, long C, long H
 }
 
 // ------------------------------------------------------------------ losses
-// kind: 0 crossentropy (probabilities, eps clamp), 1 softmax_crossentropy, 2 mse, 3 mae, 4 huber(delta)
+// kind: 0 crossentropy (probabilities, eps clamp), 1 softmax_crossentropy, 2 mse, 3 mae, 4 huber(delta),
+// 5 soft_crossentropy (param = label smoothing eps: t' = (1 - eps) t + eps / C, S = sum t',
+// loss = S lse - sum t' x, grad = S softmax - t'; any dense target, no class has to exceed 0.5)
 // targets either one-hot rows (target != null) or integer labels. Returns the mean loss; writes
 // grad (may be null) and the correct count (argmax match).
 template <typename T>
@@ -1211,7 +1360,10 @@ double loss_fused(int kind, const T* pred, const T* target, const int64_t* label
                   double param, long* correct) {
   std::vector<double> lrow(N, 0.0);
   std::vector<int> hit(N, 0);
-  const bool regression = kind >= 2;
+  if (kind < 0 || kind > 5) throw std::invalid_argument("loss_fused: unknown kind " + std::to_string(kind));
+  if (kind == 5 && !(param >= 0.0 && param < 1.0))
+    throw std::invalid_argument("loss_fused: label_smoothing " + std::to_string(param) + " is not in [0, 1)");
+  const bool regression = kind >= 2 && kind <= 4;
   const double gscale = regression ? 1.0 / ((double)N * C) : 1.0 / N;
   parallel_for(0, N, 16, [&](long lo, long hi) {
     for (long i = lo; i < hi; ++i) {
@@ -1242,6 +1394,23 @@ double loss_fused(int kind, const T* pred, const T* target, const int64_t* label
         if (hot >= 0) l = lse - p[hot];
         if (grad)
           for (long c = 0; c < C; ++c) grad[i * C + c] = (T)((std::exp((double)p[c] - lse) - tgt(c)) * gscale);
+      } else if (kind == 5) {
+        double m = p[0];
+        for (long c = 1; c < C; ++c) m = std::max(m, (double)p[c]);
+        double z = 0.0;
+        for (long c = 0; c < C; ++c) z += std::exp((double)p[c] - m);
+        const double lse = m + std::log(z);
+        const double keep = 1.0 - param, floor_ = param / (double)C;
+        double S = 0.0, dot = 0.0;
+        for (long c = 0; c < C; ++c) {
+          const double ts = keep * tgt(c) + floor_;
+          S += ts;
+          dot += ts * (double)p[c];
+        }
+        l = S * lse - dot;
+        if (grad)
+          for (long c = 0; c < C; ++c)
+            grad[i * C + c] = (T)((S * std::exp((double)p[c] - lse) - (keep * tgt(c) + floor_)) * gscale);
       } else if (kind == 0) {
         if (hot >= 0) l = -std::log(std::min(std::max((double)p[hot], param), 1.0 - param));
         if (grad)

@@ -36,6 +36,10 @@ void ThreadPool::start(int n) {
   nthreads_ = std::max(1, n);
   quit_ = false;
   quit_atomic_.store(false, std::memory_order_relaxed);
+  // workers start from the current generation: one that started from 0 in a pool that has already
+  // run jobs took a pass over the stale job slot (a null job, an old task count) and could meet
+  // the next run()'s task counter there
+  start_gen_ = generation_;
   for (int i = 1; i < nthreads_; ++i) workers_.emplace_back(&ThreadPool::worker, this, i);
 }
 
@@ -67,7 +71,7 @@ inline void cpu_relax() { __builtin_ia32_pause(); }
 }  // namespace
 
 void ThreadPool::worker(int) {
-  long seen = 0;
+  long seen = start_gen_;
   for (;;) {
     for (int i = 0, n = spin_iters(); i < n && gen_atomic_.load(std::memory_order_acquire) == seen &&
                     !quit_atomic_.load(std::memory_order_relaxed);

@@ -46,6 +46,7 @@ class ThreadPool {
   std::atomic<long> next_{0};
   std::atomic<int> active_{0};
   long generation_ = 0;
+  long start_gen_ = 0;                // generation_ when the current workers were started
   std::atomic<long> gen_atomic_{0};   // mirrors generation_ for lock-free spinning
   bool quit_ = false;
   std::atomic<bool> quit_atomic_{false};

@@ -6,3 +6,4 @@ from .datasets import (CIFAR10DataLoader, CIFAR100DataLoader, MNISTDataLoader, T
                        create_tiny_image_loader)
 from .loader import ArrayDataLoader, BaseDataLoader, SyntheticDataLoader  # noqa: F401
 from .device_loader import DeviceDataLoader, to_device_loader  # noqa: F401
+from .mix import BatchMixer  # noqa: F401

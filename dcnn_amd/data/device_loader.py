@@ -15,7 +15,9 @@ per-sample augmentation, pinned staging, H2D) is the bottleneck of a real traini
   ``nn.train._shard`` can restrict it to a rank's shard) uploaded once per epoch;
 * ``get_next_batch`` launches ``augment_batch`` on the current stream: one workgroup per sample
   gathers it, runs the augmentation chain in LDS and writes the fp32 NCHW model input and its
-  label. No host work per batch beyond the launch, no host sync, no H2D copy.
+  label. No host work per batch beyond the launch, no host sync, no H2D copy;
+* with ``set_mixer`` a second launch (``mix_batch``, csrc/kernels/mix.hip) mixes the batch with its
+  reverse in place (Mixup / CutMix) and writes the dense target that replaces the labels.
 
 The augmentation ops and their order are the reference's (``AugmentationBuilder``); their random
 draws come from a counter-based hash (``aug_uniform``), so :func:`reference_augment` below
@@ -192,6 +194,13 @@ class DeviceDataLoader(BaseDataLoader):
         self._order_dev = None
         self._order_src = None
         self.epoch = 0
+        self.mixer = None
+
+    def set_mixer(self, mixer) -> None:
+        """Mixup / CutMix (:class:`~dcnn_amd.data.mix.BatchMixer`) on every batch: ``mix_batch`` runs
+        right behind ``augment_batch`` on the same stream, and ``get_batch`` returns the dense
+        target ``[B, K]`` in place of the labels. ``None`` switches it off."""
+        self.mixer = mixer
 
     @staticmethod
     def _exact_u8(data: np.ndarray, chunk: int = 4096) -> bool:
@@ -257,6 +266,8 @@ class DeviceDataLoader(BaseDataLoader):
         self._K.augment_batch(self._data.data_ptr(), int(self.storage == "u8"), idx.data_ptr(),
                               self._labels.data_ptr(), y.data_ptr(), x.data_ptr(), len(idx), C, H, W,
                               self.seed_for_epoch(), device_ops(self.augmentation, C), stream_ptr(self.dev))
+        if self.mixer is not None:
+            return self.mixer(x, y)
         if self.one_hot:
             y = torch.nn.functional.one_hot(y, self.num_classes).float().view(len(idx), self.num_classes, 1, 1)
         return x, y

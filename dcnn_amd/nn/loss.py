@@ -23,6 +23,8 @@ _ALIASES = {
     "mse": "mse", "mean_squared_error": "mse",
     "mae": "mae", "mean_absolute_error": "mae",
     "huber": "huber",
+    "soft_crossentropy": "soft_crossentropy", "soft_ce": "soft_crossentropy",
+    "label_smoothing_ce": "soft_crossentropy",
 }
 
 
@@ -133,6 +135,45 @@ class LogSoftmaxCrossEntropyLoss(SoftmaxCrossEntropyLoss):
     kind = "logsoftmax_crossentropy"
 
 
+class SoftTargetCrossEntropyLoss(Loss):
+    """Cross entropy on logits against any dense target (Mixup / CutMix rows, or labels), with label
+    smoothing: ``t' = (1 - eps) t + eps / C``, ``S = sum_c t'``, loss ``= mean_n(S lse - sum_c t' x)``,
+    gradient ``(S softmax(x) - t') / N``. Unlike the other cross entropies it never looks for a
+    class above 0.5, so the loss of a mixed target is the real one."""
+    kind = "soft_crossentropy"
+
+    def __init__(self, label_smoothing: float = 0.0):
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        super().__init__(label_smoothing)
+
+    @property
+    def label_smoothing(self) -> float:
+        return self.param
+
+    def get_config(self) -> LossConfig:
+        return LossConfig(self.kind, self.kind, {"label_smoothing": self.param})
+
+    def clone(self):
+        return type(self)(self.param)
+
+    def _smooth(self, p, t):
+        if t.dtype in (torch.int64, torch.int32) and t.dim() == 1:
+            t = torch.nn.functional.one_hot(t.long(), p.shape[1])
+        t = self._2d(t).double()
+        return (1.0 - self.param) * t + self.param / p.shape[1]
+
+    def _cpu_loss(self, p, t):
+        ts = self._smooth(p, t)
+        lse = torch.logsumexp(p.double(), 1)
+        return ((ts.sum(1) * lse - (ts * p.double()).sum(1)).sum() / p.shape[0]).to(p.dtype)
+
+    def _cpu_grad(self, p, t):
+        ts = self._smooth(p, t)
+        return ((ts.sum(1, keepdim=True) * torch.softmax(p.double(), 1) - ts) / p.shape[0]).to(p.dtype)
+
+
 class MSELoss(Loss):
     kind = "mse"
 
@@ -184,6 +225,8 @@ class LossFactory:
             return SoftmaxCrossEntropyLoss()
         if k == "logsoftmax_crossentropy":
             return LogSoftmaxCrossEntropyLoss()
+        if k == "soft_crossentropy":
+            return SoftTargetCrossEntropyLoss(kw.get("label_smoothing", 0.0))
         if k == "mse":
             return MSELoss()
         if k == "mae":
@@ -198,12 +241,15 @@ class LossFactory:
             return CrossEntropyLoss(p.get("param", p.get("epsilon", 1e-15)))
         if _ALIASES.get(t) == "huber":
             return HuberLoss(p.get("param", p.get("delta", 1.0)))
+        if _ALIASES.get(t) == "soft_crossentropy":
+            return SoftTargetCrossEntropyLoss(p.get("label_smoothing", p.get("param", 0.0)))
         return LossFactory.create(t)
 
     # reference-named helpers
     create_crossentropy = staticmethod(lambda epsilon=1e-15: CrossEntropyLoss(epsilon))
     create_softmax_crossentropy = staticmethod(lambda: SoftmaxCrossEntropyLoss())
     create_logsoftmax_crossentropy = staticmethod(lambda: LogSoftmaxCrossEntropyLoss())
+    create_soft_crossentropy = staticmethod(lambda label_smoothing=0.0: SoftTargetCrossEntropyLoss(label_smoothing))
     create_mse = staticmethod(lambda: MSELoss())
     create_mae = staticmethod(lambda: MAELoss())
     create_huber = staticmethod(lambda delta=1.0: HuberLoss(delta))

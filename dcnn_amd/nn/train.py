@@ -52,6 +52,11 @@ class TrainingConfig:
     bucket_mb: float = 4.0          # DP all-reduce bucket size (small trailing bucket = little exposed comm)
     snapshot_dir: str = "model_snapshots"
     max_batches_per_epoch: int = 0  # 0 = full epoch
+    mixup_alpha: float = 0.0        # Mixup / CutMix (data/mix.py BatchMixer): built when an alpha is > 0
+    cutmix_alpha: float = 0.0
+    mix_prob: float = 1.0
+    mix_switch_prob: float = 0.5
+    label_smoothing: float = 0.0    # of the soft_crossentropy loss (examples build the loss from it)
 
     def load_from_env(self) -> "TrainingConfig":
         self.epochs = get_env("EPOCHS", DEFAULT_EPOCH)
@@ -65,6 +70,11 @@ class TrainingConfig:
         self.num_microbatches = get_env("NUM_MICROBATCHES", 2)
         self.device_type = get_env("DEVICE_TYPE", "CPU").upper()
         self.use_graph = get_env("USE_HIPGRAPH", True)
+        self.mixup_alpha = get_env("MIXUP_ALPHA", 0.0)
+        self.cutmix_alpha = get_env("CUTMIX_ALPHA", 0.0)
+        self.mix_prob = get_env("MIX_PROB", 1.0)
+        self.mix_switch_prob = get_env("MIX_SWITCH_PROB", 0.5)
+        self.label_smoothing = get_env("LABEL_SMOOTHING", 0.0)
         return self
 
     def print_config(self) -> None:
@@ -102,12 +112,33 @@ def _shard(loader):
         loader.order = loader.order[:n][r::w].copy()
 
 
+def _check_mixer_loss(loss_function) -> None:
+    if getattr(loss_function, "kind", None) != "soft_crossentropy":
+        raise ValueError(f"Mixup / CutMix needs the soft_crossentropy loss, got {getattr(loss_function, 'kind', '?')}: "
+                         "every other loss takes its value from the class whose target is above 0.5, so the "
+                         "reported loss of a mixed target would be silently wrong")
+
+
+def build_mixer(config: "TrainingConfig", num_classes: int, seed: int = 0):
+    """The :class:`~dcnn_amd.data.mix.BatchMixer` of ``config`` (None when both alphas are 0)."""
+    if config.mixup_alpha <= 0 and config.cutmix_alpha <= 0:
+        return None
+    from ..data.mix import BatchMixer
+    return BatchMixer(num_classes, config.mixup_alpha, config.cutmix_alpha, config.mix_prob, config.mix_switch_prob,
+                      seed)
+
+
 def train_class_epoch(model, train_loader, optimizer, loss_function, config: Optional[TrainingConfig] = None,
-                      step=None, metrics=None) -> tuple:
+                      step=None, metrics=None, mixer=None) -> tuple:
     """One epoch; returns (avg loss, accuracy). ``step`` is a prebuilt ``TrainStep``; ``metrics``
-    a :class:`~dcnn_amd.utils.metrics.MetricsSink` that gets a record per print interval."""
+    a :class:`~dcnn_amd.utils.metrics.MetricsSink` that gets a record per print interval. ``mixer``
+    (a :class:`~dcnn_amd.data.mix.BatchMixer`, for host loaders): applied to every batch after the
+    device copy; needs the ``soft_crossentropy`` loss. An HBM-resident loader mixes by itself
+    (``DeviceDataLoader.set_mixer``)."""
     from ..runtime.step import TrainStep
     config = config or TrainingConfig()
+    if mixer is not None or getattr(train_loader, "mixer", None) is not None:
+        _check_mixer_loss(loss_function)
     model.set_training(True)
     train_loader.reset()
     _shard(train_loader)
@@ -122,6 +153,10 @@ def train_class_epoch(model, train_loader, optimizer, loss_function, config: Opt
             break
         x, y = b
         x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
+        if mixer is not None:
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                x = x.float().contiguous()
+            x, y = mixer(x, y.argmax(1).reshape(-1) if y.dim() > 1 else y)
         n = x.shape[0]
         if step.use_graph and graph_bs is None:
             graph_bs = n
@@ -167,9 +202,12 @@ def validate_class_model(model, test_loader, loss_function, max_batches: int = 0
     return acc.result()
 
 
-def save_checkpoint(model, optimizer, path: str, epoch: int = 0, extra: Optional[dict] = None) -> None:
-    """Reference-format weights (.json/.bin) + .state sidecar (BN stats, optimizer, epoch, LR)."""
+def save_checkpoint(model, optimizer, path: str, epoch: int = 0, extra: Optional[dict] = None, mixer=None) -> None:
+    """Reference-format weights (.json/.bin) + .state sidecar (BN stats, optimizer, epoch, LR, and
+    the step counter of ``mixer``, a BatchMixer, when given)."""
     state = {"epoch": int(epoch), "learning_rate": float(optimizer.get_learning_rate()) if optimizer else 0.0}
+    if mixer is not None:
+        state["mixer:state"] = int(mixer.state)
     if optimizer is not None:
         for k, v in optimizer.state_dict().items():
             state[f"optimizer:{k}"] = v
@@ -179,10 +217,13 @@ def save_checkpoint(model, optimizer, path: str, epoch: int = 0, extra: Optional
     model.save_state(path + ".state", extra=state)
 
 
-def load_checkpoint(model, optimizer, path: str) -> int:
-    """Restore weights, BN statistics and optimizer state; returns the saved epoch."""
+def load_checkpoint(model, optimizer, path: str, mixer=None) -> int:
+    """Restore weights, BN statistics and optimizer state (and ``mixer``'s step counter); returns the
+    saved epoch."""
     model.load_weights_file(path + ".bin")
     st = model.load_state(path + ".state") if os.path.exists(path + ".state") else {}
+    if mixer is not None and "mixer:state" in st:
+        mixer.state = int(st["mixer:state"])
     if optimizer is not None and st:
         if not optimizer.params:
             optimizer.attach(model)
@@ -194,9 +235,12 @@ def load_checkpoint(model, optimizer, path: str) -> int:
 
 def train_classification_model(model, train_loader, test_loader, optimizer, loss_function,
                                config: Optional[TrainingConfig] = None, scheduler=None, data_parallel=None,
-                               start_epoch: int = 0, metrics=None) -> list:
+                               start_epoch: int = 0, metrics=None, mixer=None) -> list:
     """Epoch loop (reference include/nn/train.hpp:191-268). ``metrics``: a MetricsSink (default:
-    one on ``METRICS_FILE`` when set) receiving per-interval and per-epoch JSON records."""
+    one on ``METRICS_FILE`` when set) receiving per-interval and per-epoch JSON records. ``mixer``:
+    a BatchMixer; by default one is built from the config when ``mixup_alpha`` or ``cutmix_alpha`` is
+    > 0 (an HBM-resident loader gets it through ``set_mixer``, a host loader is mixed after the device
+    copy). Mixing needs the ``soft_crossentropy`` loss; validation keeps integer labels."""
     from ..parallel.dp import DataParallel
     from ..runtime.step import TrainStep
     from ..utils.metrics import MetricsSink
@@ -204,6 +248,17 @@ def train_classification_model(model, train_loader, test_loader, optimizer, loss
     if not model.initialized:
         model.initialize()
     rank = dist.get_rank() if dist.is_initialized() else 0
+    if mixer is None:
+        nc = int(getattr(train_loader, "num_classes", 0) or 0)
+        if (config.mixup_alpha > 0 or config.cutmix_alpha > 0) and nc < 1:
+            raise ValueError("Mixup / CutMix: the training loader does not know its number of classes; pass a mixer")
+        mixer = build_mixer(config, nc, seed=rank)
+    host_mixer = mixer
+    if mixer is not None:
+        _check_mixer_loss(loss_function)
+        if hasattr(train_loader, "set_mixer"):
+            train_loader.set_mixer(mixer)
+            host_mixer = None
     dp = data_parallel or DataParallel(model, bucket_mb=config.bucket_mb)
     optimizer.attach(model)
     train_loader.prepare_batches(config.batch_size)
@@ -222,7 +277,7 @@ def train_classification_model(model, train_loader, test_loader, optimizer, loss
             print(f"Epoch {epoch + 1}/{config.epochs}", flush=True)
         t0 = time.perf_counter()
         tr_loss, tr_acc = train_class_epoch(model, train_loader, optimizer, loss_function, config, step,
-                                            metrics if rank == 0 else None)
+                                            metrics if rank == 0 else None, mixer=host_mixer)
         if model.device.is_gpu():
             torch.cuda.synchronize()
         train_ms = (time.perf_counter() - t0) * 1e3
@@ -241,7 +296,7 @@ def train_classification_model(model, train_loader, test_loader, optimizer, loss
                 print(f"New best validation accuracy: {best * 100:.2f}%")
                 path = os.path.join(config.snapshot_dir, model.name())
                 try:
-                    save_checkpoint(model, optimizer, path, epoch + 1)
+                    save_checkpoint(model, optimizer, path, epoch + 1, mixer=mixer)
                     print(f"Model saved to {path}")
                 except OSError as e:
                     print(f"Error saving model: {e}")

@@ -19,7 +19,7 @@ from ._ext import native
 _DT = {torch.float32: 0, torch.float64: 1}
 ACT_CODES = {"linear": 0, "relu": 1, "leaky_relu": 2, "elu": 3, "sigmoid": 4, "tanh": 5, "gelu": 6}
 LOSS_CODES = {"crossentropy": 0, "softmax_crossentropy": 1, "logsoftmax_crossentropy": 1, "mse": 2, "mae": 3,
-              "huber": 4}
+              "huber": 4, "soft_crossentropy": 5}
 
 
 def C():
@@ -504,6 +504,33 @@ def adam_step_nodecay(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, decoupled, nod
     C().adam_step_nodecay(dt(p_), p_.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p_.numel(), float(lr),
                           float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled),
                           nodecay.data_ptr())
+
+
+def mix_plan(seed: int, step: int, H: int, W: int, mixup_alpha: float, cutmix_alpha: float, prob: float = 1.0,
+             switch_prob: float = 0.5):
+    """The Mixup / CutMix draw of training batch ``step`` (from 1): ``(mode, lam, yl, yh, xl, xh)``,
+    mode 0 none / 1 Mixup / 2 CutMix. A pure function of its arguments (csrc/native mix_plan), the
+    one both front ends call."""
+    return tuple(C().mix_plan(int(seed) & ((1 << 64) - 1), int(step) & ((1 << 64) - 1), int(H), int(W),
+                              float(mixup_alpha), float(cutmix_alpha), float(prob), float(switch_prob)))
+
+
+def mix_batch(x, labels, target, mode, lam, box, num_classes):
+    """Mixup (mode 1) / CutMix (mode 2, ``box = (yl, yh, xl, xh)``) of ``x`` [B, C, H, W] with its
+    reversed batch, in place, and the dense float32 ``target`` [B, K] written whole. The rounding is
+    the GPU kernel's: the two backends agree bit for bit."""
+    if x.dim() != 4 or not x.is_contiguous() or x.is_cuda:
+        raise ValueError("mix_batch: x is a contiguous CPU [B, C, H, W] tensor")
+    B, Cn, H, W = x.shape
+    K = int(num_classes)
+    C().mix_check(B, Cn, H, W, K, int(mode), float(lam), *map(int, box))
+    if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous():
+        raise ValueError("mix_batch: labels are int64 [B]")
+    if target.dtype != torch.float32 or target.shape != (B, K) or not target.is_contiguous():
+        raise ValueError("mix_batch: target is a contiguous float32 [B, num_classes] tensor")
+    C().mix_batch(dt(x), x.data_ptr(), labels.data_ptr(), target.data_ptr(), B, Cn, H, W, int(mode), float(lam),
+                  *map(int, box), K)
+    return x, target
 
 
 def drop_path_mask(seed: int, draw: int, n: int, p_drop: float) -> torch.Tensor:

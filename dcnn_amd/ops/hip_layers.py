@@ -291,7 +291,7 @@ def lscale_drop_bwd(dy, x, gamma, mask, dgamma):
 
 # ------------------------------------------------------------------------------ loss / optim
 LOSS_CODES = {"crossentropy": 0, "softmax_crossentropy": 1, "logsoftmax_crossentropy": 2, "mse": 3, "mae": 4,
-              "huber": 5}
+              "huber": 5, "soft_crossentropy": 6}
 
 
 def loss_fused(pred2d, target2d=None, labels=None, kind="softmax_crossentropy", param=1e-15, want_grad=True,
@@ -314,6 +314,23 @@ def loss_fused(pred2d, target2d=None, labels=None, kind="softmax_crossentropy", 
                  correct.data_ptr(), N, C, LOSS_CODES[kind], float(param), float(grad_scale), ptr(ws), ptr(tk),
                  stream_ptr())
     return loss, grad, correct
+
+
+def mix_batch(x, labels, target, mode, lam, box, num_classes):
+    """Mixup / CutMix of the fp32 NCHW device batch ``x`` with its reversed batch, in place, plus the
+    dense float32 ``target`` [B, K]: one launch on the current stream, no host sync (mix.hip)."""
+    if x.dim() != 4 or x.dtype != F32 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("mix_batch: x is a contiguous float32 GPU [B, C, H, W] tensor")
+    B, C, H, W = x.shape
+    K = int(num_classes)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_cuda or not labels.is_contiguous():
+        raise ValueError("mix_batch: labels are int64 [B] on the GPU")
+    if (K >= 1 and tuple(target.shape) != (B, K)) or target.dtype != F32 or not target.is_cuda \
+            or not target.is_contiguous():
+        raise ValueError("mix_batch: target is a contiguous float32 GPU [B, num_classes] tensor")
+    kernels().mix_batch(x.data_ptr(), labels.data_ptr(), target.data_ptr(), B, C, H, W, int(mode), float(lam),
+                        *map(int, box), K, stream_ptr(x.device))
+    return x, target
 
 
 def adam_step(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, wd, decoupled, hyper=None, nodecay=None):

@@ -17,6 +17,7 @@
 //                                              one stride-2 basic residual block, forward + backward on
 //                                              fixed data; its input gradient and parameter gradients
 //   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph] [--adamw-no-decay]
+//                         [--mix] [--switch-to-labels]
 //                                              Adam steps on a synthetic set, then save
 //   grads / train also take [--drop-path RATE] [--seed-drop-path] (ConvNeXt models)
 // Output is plain text: one "key v0 v1 ..." line per item.
@@ -149,7 +150,12 @@ int main(int argc, char** argv) {
       const int batch = std::atoi(argv[3]);
       const int hw = input_hw(argv[2]), classes = num_classes(argv[2]);
       SyntheticClassification data((size_t)batch, 3, hw, hw, classes, 5, 0.3f);
-      Loss loss = LossFactory::create("softmax_crossentropy");
+      // --mix: every batch through a BatchMixer (Mixup 0.8 / CutMix 1.0, seed 7), trained against its
+      // dense target with soft_crossentropy (label smoothing 0.1); --switch-to-labels: the last step
+      // is fed the integer labels instead (a captured step must refuse them)
+      const bool mix = flag_arg(argc, argv, "--mix"), sw = flag_arg(argc, argv, "--switch-to-labels");
+      BatchMixer mixer(classes, 0.8, 1.0, 1.0, 0.5, 7);
+      Loss loss = mix ? LossFactory::create("soft_crossentropy", 0.1f) : LossFactory::create("softmax_crossentropy");
       data.reset(0);
       Tensor x, y;
       if (!data.next(batch, x, y)) throw std::runtime_error("no batch");
@@ -350,7 +356,12 @@ int main(int argc, char** argv) {
       const bool nd = flag_arg(argc, argv, "--adamw-no-decay");
       Adam opt(1e-3f, 0.9f, 0.999f, 1e-8f, nd ? 0.1f : 0.f, nd);
       opt.set_no_decay_norm_bias(nd);
-      Loss loss = LossFactory::create("softmax_crossentropy");
+      // --mix: every batch through a BatchMixer (Mixup 0.8 / CutMix 1.0, seed 7), trained against its
+      // dense target with soft_crossentropy (label smoothing 0.1); --switch-to-labels: the last step
+      // is fed the integer labels instead (a captured step must refuse them)
+      const bool mix = flag_arg(argc, argv, "--mix"), sw = flag_arg(argc, argv, "--switch-to-labels");
+      BatchMixer mixer(classes, 0.8, 1.0, 1.0, 0.5, 7);
+      Loss loss = mix ? LossFactory::create("soft_crossentropy", 0.1f) : LossFactory::create("softmax_crossentropy");
       data.reset(0);
       Tensor x, y;
       bool graph = false;  // --graph: the GPU step captured once (TrainGraph) and replayed
@@ -358,6 +369,12 @@ int main(int argc, char** argv) {
       TrainGraph tg(m, opt, loss);
       std::printf("losses");
       for (int i = 0; i < steps && data.next(batch, x, y); ++i) {
+        if (mix && !(sw && i == steps - 1)) {
+          Tensor xd = x.to(dev).clone(), t;
+          mixer.mix(xd, y, t);
+          x = xd;
+          y = t;
+        }
         if (graph && dev.is_gpu()) {
           tg.step(x, y);
           std::printf(" %.6g", tg.last_loss());
