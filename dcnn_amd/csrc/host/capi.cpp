@@ -313,4 +313,73 @@ int dcnn_c_layer_scale_drop_bwd(const void* dy, const void* x, const float* gamm
   return guarded([&] { gpu_ops::layer_scale_drop_bwd(dy, x, gamma, mask, dx, dgamma, R, C, rows_per_sample); });
 }
 
+// Global-norm clipping and weight EMA over flat fp32 buffers. Device: out4 = {sumsq, norm, coef,
+// max_norm}; the steps take optional inputs, null = off: nodecay (one byte per 64 elements), coef (a
+// device pointer, e.g. out4 + 2; g itself is not rewritten), ema with its decay; shadow (bf16) may
+// be null. hp = {lr, b1, b2, eps, bc1, bc2, wd} for Adam, {lr, momentum} for SGD.
+int dcnn_c_grad_sumsq(const float* g, long n, float max_norm, float* out4) {
+  return guarded([&] { gpu_ops::grad_sumsq(g, n, max_norm, out4); });
+}
+
+int dcnn_c_adam_tail(float* p, const float* g, float* m, float* v, void* shadow, long n, const float* hp, int decoupled,
+                     const uint8_t* nodecay, const float* coef, float* ema, float decay) {
+  return guarded([&] {
+    gpu_ops::adam_tail(p, g, m, v, shadow, n, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], decoupled != 0, nullptr,
+                       nodecay, coef, ema, decay);
+  });
+}
+
+int dcnn_c_sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, const float* hp, const float* coef,
+                    float* ema, float decay) {
+  return guarded([&] { gpu_ops::sgd_tail(p, g, vel, shadow, n, hp[0], hp[1], coef, ema, decay); });
+}
+
+int dcnn_c_ema_swap(float* a, float* b, void* shadow, long n) {
+  return guarded([&] { gpu_ops::ema_swap(a, b, shadow, n); });
+}
+
+// the same on the CPU backend, host pointers: *sumsq the sum of g^2; coef null = no clipping
+int dcnn_c_grad_sumsq_host(const float* g, long n, double* sumsq) {
+  try {
+    *sumsq = cpu_ops::grad_sumsq(g, n);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+int dcnn_c_adam_tail_host(float* p, const float* g, float* m, float* v, long n, const float* hp, int decoupled,
+                          const uint8_t* nodecay, const double* coef, float* ema, float decay) {
+  try {
+    cpu_ops::adam_tail(p, g, m, v, n, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], decoupled != 0, nodecay, coef,
+                       ema, decay);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+int dcnn_c_sgd_tail_host(float* p, const float* g, float* vel, long n, const float* hp, const double* coef, float* ema,
+                         float decay) {
+  try {
+    cpu_ops::sgd_tail(p, g, vel, n, hp[0], hp[1], coef, ema, decay);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+int dcnn_c_ema_swap_host(float* a, float* b, long n) {
+  try {
+    cpu_ops::ema_swap(a, b, n);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
 }  // extern "C"

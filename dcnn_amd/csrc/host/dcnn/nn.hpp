@@ -19,6 +19,7 @@
 // include/nn/train.hpp:202 (train_classification_model), include/nn/optimizers.hpp,
 // include/nn/loss.hpp, examples/mnist_cnn_trainer.cpp.
 #pragma once
+#include <cmath>
 #include <functional>
 #include <map>
 #include <memory>
@@ -41,6 +42,7 @@ struct Param {
   Layout layout = Layout::NCHW;
   Tensor value, grad, shadow;
   Tensor m, v;  // optimizer state (lazily created)
+  Tensor ema;   // weight EMA of the per-parameter path (an optimizer with set_ema_decay; lazily created)
   // excluded from weight decay when the optimizer's no_decay_norm_bias is on: set by the owning
   // layer for biases, norm affines and layer scales (by kind, never by shape)
   bool no_decay = false;
@@ -56,6 +58,9 @@ struct ParamArena {
   // one byte per 64-element block, 1 where the block belongs to a Param with no_decay (built once
   // by Sequential::pack_params: static, so a captured optimizer step replays it as it is)
   Tensor nodecay;
+  // weight EMA (an optimizer with set_ema_decay): a flat buffer of n floats, a copy of `value` when
+  // it is created, updated inside the fused step; undefined while the EMA is off
+  Tensor ema;
   // every eligible conv's dgrad operand ([C][KH][KW][Co] bf16), regenerated from the shadows in
   // one batched launch after each fused optimizer step (rows: src, dst, Co, T, C)
   Tensor wt_table;
@@ -691,9 +696,37 @@ class Optimizer {
   virtual void step(const std::vector<Param*>& params) = 0;
   void set_learning_rate(float lr) { lr_ = lr; }
   float learning_rate() const { return lr_; }
+  // Global-norm gradient clipping (torch's clip_grad_norm_, L2): the step takes g * coef with
+  // coef = min(1, max_norm / (norm + 1e-6)) over ALL parameters; the gradient tensors are not
+  // rewritten. On a GPU arena the norm stays in device memory (one fixed-order reduction, no host
+  // read), so a captured step remains one graph. A non-finite norm propagates; no step is skipped.
+  // 0 = off (the default): the step launches what it always launched.
+  void set_max_grad_norm(float max_norm);
+  float max_grad_norm() const { return max_norm_; }
+  // Weight EMA, decay in (0, 1): ema = decay ema + (1 - decay) p_new after each step, a copy of the
+  // weights when it is created (prepare(), or the first step). BatchNorm running statistics are
+  // not averaged. 0 = off.
+  void set_ema_decay(float decay);
+  float ema_decay() const { return ema_decay_; }
+  // create what the switches need (EMA buffers, the norm block, the reduction's workspace) now;
+  // step() does it on demand, a graph capture needs it done before
+  void prepare(const std::vector<Param*>& params);
+  // exchange the weights with their EMA (and back with a second call, bit for bit); refreshes the
+  // bf16 shadows and the transposed conv operands. Between steps only; no-op with the EMA off.
+  void swap_ema(const std::vector<Param*>& params);
+  // the gradient norm of the last step before clipping (synchronises the device); NaN with clipping off
+  float last_grad_norm() const;
 
  protected:
+  bool tail() const { return max_norm_ > 0.f || ema_decay_ > 0.f; }
+  // GPU arena: launch the norm reduction, return the device pointer to coef (null with clipping off)
+  const float* launch_norm(ParamArena* a);
+  // per-parameter path: the coefficient from the norm over all parameters (false with clipping off)
+  bool host_coef(const std::vector<Param*>& params, double* coef);
   float lr_;
+  float max_norm_ = 0.f, ema_decay_ = 0.f;
+  Tensor norm_;                      // device {sumsq, norm, coef, max_norm} (GPU arena path)
+  float host_norm_ = std::nanf("");  // per-parameter path
 };
 
 class SGD : public Optimizer {

@@ -81,6 +81,16 @@ void sgd(float* p, const float* g, float* vel, long n, float lr, float momentum)
 // with wd = 0 (a parameter smaller than 64 elements: one byte)
 void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                   float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
+// global-norm clipping and weight EMA: the sum of g^2 (fixed order, double partials), and the steps
+// with optional inputs, null = off: nodecay (as above), coef (the step takes g * coef and leaves g as
+// it is), ema (ema = decay ema + (1 - decay) p_new); ema_swap exchanges two buffers
+double grad_sumsq(const float* g, long n);
+void adam_tail(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float bc1,
+               float bc2, float wd, bool decoupled, const uint8_t* nodecay, const double* coef, float* ema,
+               float decay);
+void sgd_tail(float* p, const float* g, float* vel, long n, float lr, float momentum, const double* coef, float* ema,
+              float decay);
+void ema_swap(float* a, float* b, long n);
 // stochastic depth: mask[n] = 0 or 1 / (1 - p) from (seed, draw), the one function of the kernel
 // library and the native backend; y[n][:] = mask[n] x[n][:] over samples of `row` elements
 void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw);
@@ -330,6 +340,20 @@ void adam_nodecay(float* p, const float* g, float* m, float* v, void* shadow, lo
                   float eps, float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
 void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2,
                       float eps, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay);
+// global-norm clipping and weight EMA (loss_optim.hip). grad_norm_workspace: the per-workgroup
+// partials and the self-resetting ticket word of grad_sumsq for n elements, created and zeroed
+// outside any capture. grad_sumsq: out[4] = {sumsq, norm, coef, max_norm} on the device, one launch,
+// fixed order. The tail steps take optional device inputs, null = off: nodecay, coef (a pointer to
+// the coefficient; g itself is not rewritten) and ema with its decay. ema_swap: a <-> b, shadow
+// (optional) = bf16 of the new a.
+void grad_norm_workspace(long n);
+void grad_sumsq(const float* g, long n, float max_norm, float* out);
+void adam_tail(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
+               float eps, float bc1, float bc2, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay,
+               const float* coef, float* ema, float decay);
+void sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum, const float* coef,
+              float* ema, float decay);
+void ema_swap(float* a, float* b, void* shadow, long n);
 // stochastic depth (droppath.hip, bf16 activations). drop_path_draw: *slot = ++*ctr on the device,
 // then the mask of (seed, *slot) into mask[N] (a captured step draws a new mask at every replay);
 // drop_path_mask: the mask of a given draw index. drop_path_scale: y[n] = mask[n] x[n] (+ residual)

@@ -2263,18 +2263,93 @@ ParamArena* whole_arena(const std::vector<Param*>& params) {
 }
 }  // namespace
 
-void SGD::step(const std::vector<Param*>& params) {
+void Optimizer::set_max_grad_norm(float max_norm) {
+  if (!(max_norm >= 0.f) || std::isinf(max_norm))
+    throw std::invalid_argument("max_grad_norm " + std::to_string(max_norm) + " is not a finite value >= 0");
+  max_norm_ = max_norm;
+}
+
+void Optimizer::set_ema_decay(float decay) {
+  if (!(decay >= 0.f && decay < 1.f))
+    throw std::invalid_argument("ema_decay " + std::to_string(decay) + " is not in [0, 1)");
+  ema_decay_ = decay;
+}
+
+void Optimizer::prepare(const std::vector<Param*>& params) {
+  if (!tail()) return;
   if (ParamArena* a = whole_arena(params)) {
-    gpu_ops::sgd(a->value.ptr<float>(), a->grad.ptr<float>(), momentum_ != 0.f ? a->m.ptr<float>() : nullptr,
-                 a->shadow.data(), (long)a->n, lr_, momentum_);
+    if (ema_decay_ > 0.f && !a->ema.defined()) a->ema = a->value.clone();
+    if (max_norm_ > 0.f) {
+      if (!norm_.defined()) norm_ = Tensor::zeros({4}, DType::F32, a->value.device());
+      gpu_ops::grad_norm_workspace((long)a->n);
+    }
+    return;
+  }
+  for (auto* p : params) {
+    if (p->value.device().is_gpu())
+      throw std::runtime_error("gradient clipping / weight EMA on the GPU need all parameters of one arena");
+    if (ema_decay_ > 0.f && !p->ema.defined()) p->ema = p->value.clone();
+  }
+}
+
+const float* Optimizer::launch_norm(ParamArena* a) {
+  if (!(max_norm_ > 0.f)) return nullptr;
+  gpu_ops::grad_sumsq(a->grad.ptr<float>(), (long)a->n, max_norm_, norm_.ptr<float>());
+  return norm_.ptr<float>() + 2;
+}
+
+bool Optimizer::host_coef(const std::vector<Param*>& params, double* coef) {
+  if (!(max_norm_ > 0.f)) return false;
+  double sumsq = 0.0;  // over all parameters, before any of them is stepped
+  for (auto* p : params) sumsq += cpu_ops::grad_sumsq(p->grad.ptr<float>(), p->value.numel());
+  const double norm = std::sqrt(sumsq), c = max_norm_ / (norm + 1e-6);
+  host_norm_ = (float)norm;
+  *coef = c < 1.0 || c != c ? c : 1.0;
+  return true;
+}
+
+float Optimizer::last_grad_norm() const {
+  if (!(max_norm_ > 0.f)) return std::nanf("");
+  if (!norm_.defined()) return host_norm_;
+  gpu::flow_synchronize();
+  float h[4];
+  gpu::copy(h, norm_.data(), sizeof h, 1);
+  return h[1];
+}
+
+void Optimizer::swap_ema(const std::vector<Param*>& params) {
+  if (!(ema_decay_ > 0.f)) return;
+  prepare(params);
+  if (ParamArena* a = whole_arena(params)) {
+    gpu_ops::ema_swap(a->value.ptr<float>(), a->ema.ptr<float>(), a->shadow.data(), (long)a->n);
     a->refresh_transposes();
     return;
   }
+  for (auto* p : params) cpu_ops::ema_swap(p->value.ptr<float>(), p->ema.ptr<float>(), p->value.numel());
+}
+
+void SGD::step(const std::vector<Param*>& params) {
+  if (tail()) prepare(params);
+  if (ParamArena* a = whole_arena(params)) {
+    float* vel = momentum_ != 0.f ? a->m.ptr<float>() : nullptr;
+    if (tail())
+      gpu_ops::sgd_tail(a->value.ptr<float>(), a->grad.ptr<float>(), vel, a->shadow.data(), (long)a->n, lr_, momentum_,
+                        launch_norm(a), ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_);
+    else
+      gpu_ops::sgd(a->value.ptr<float>(), a->grad.ptr<float>(), vel, a->shadow.data(), (long)a->n, lr_, momentum_);
+    a->refresh_transposes();
+    return;
+  }
+  double coef = 1.0;
+  const bool clip = host_coef(params, &coef);
   for (auto* p : params) {
     if (p->arena) p->arena->wt_valid = false;  // (the convs transpose their own operand)
     if (momentum_ != 0.f && !p->m.defined()) p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
     float* vel = momentum_ != 0.f ? p->m.ptr<float>() : nullptr;
-    if (p->value.device().is_gpu())
+    if (tail())  // (CPU parameters: prepare() refused any other)
+      cpu_ops::sgd_tail(p->value.ptr<float>(), p->grad.ptr<float>(), vel, p->value.numel(), lr_, momentum_,
+                        clip ? &coef : nullptr, ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_);
+    else if (p->value.device().is_gpu())
       gpu_ops::sgd(p->value.ptr<float>(), p->grad.ptr<float>(), vel, p->shadow.data(), p->value.numel(), lr_,
                    momentum_);
     else
@@ -2300,6 +2375,7 @@ void Adam::before_replay() {
 }
 
 void Adam::step(const std::vector<Param*>& params) {
+  if (tail()) prepare(params);
   if (ParamArena* a = whole_arena(params)) {
     // step scalars on the device (a captured step replays with the current lr and t)
     if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
@@ -2310,7 +2386,12 @@ void Adam::step(const std::vector<Param*>& params) {
     ++t_;
     ++hyper_t_;
     gpu_ops::adam_hyper_step(hyper_.ptr<float>(), b1_, b2_);
-    if (no_decay_)
+    if (tail())
+      gpu_ops::adam_tail(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
+                         a->shadow.data(), (long)a->n, 0.f, b1_, b2_, eps_, 1.f, 1.f, wd_, decoupled_,
+                         hyper_.ptr<float>(), no_decay_ ? static_cast<const uint8_t*>(a->nodecay.data()) : nullptr,
+                         launch_norm(a), ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_);
+    else if (no_decay_)
       gpu_ops::adam_dev_nodecay(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
                                 a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>(),
                                 static_cast<const uint8_t*>(a->nodecay.data()));
@@ -2322,6 +2403,8 @@ void Adam::step(const std::vector<Param*>& params) {
   }
   ++t_;
   const float bc1 = 1.f - std::pow(b1_, (float)t_), bc2 = 1.f - std::pow(b2_, (float)t_);
+  double coef = 1.0;
+  const bool clip = host_coef(params, &coef);
   for (auto* p : params) {
     if (p->arena) p->arena->wt_valid = false;
     if (!p->m.defined()) {
@@ -2329,7 +2412,11 @@ void Adam::step(const std::vector<Param*>& params) {
       p->v = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
     }
     const float wd = no_decay_ && p->no_decay ? 0.f : wd_;  // (per parameter: the flag itself, no table)
-    if (p->value.device().is_gpu())
+    if (tail())  // (CPU parameters: prepare() refused any other)
+      cpu_ops::adam_tail(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
+                         p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_, nullptr,
+                         clip ? &coef : nullptr, ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_);
+    else if (p->value.device().is_gpu())
       gpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
                     p->shadow.data(), p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
     else

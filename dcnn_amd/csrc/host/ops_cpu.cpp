@@ -185,5 +185,20 @@ void sgd(float* p, const float* g, float* vel, long n, float lr, float momentum)
   C::sgd_step(p, g, vel, n, lr, momentum);
 }
 
+double grad_sumsq(const float* g, long n) { return C::grad_sumsq<float>(g, n); }
+
+void adam_tail(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float bc1,
+               float bc2, float wd, bool decoupled, const uint8_t* nodecay, const double* coef, float* ema,
+               float decay) {
+  C::adam_step_tail<float>(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nodecay, coef, ema, decay);
+}
+
+void sgd_tail(float* p, const float* g, float* vel, long n, float lr, float momentum, const double* coef, float* ema,
+              float decay) {
+  C::sgd_step_tail<float>(p, g, vel, n, lr, momentum, coef, ema, decay);
+}
+
+void ema_swap(float* a, float* b, long n) { C::ema_swap<float>(a, b, n); }
+
 }  // namespace cpu_ops
 }  // namespace dcnn

@@ -344,7 +344,7 @@ inline hipStream_t cur() { return static_cast<hipStream_t>(gpu::flow()); }
 
 // grow-only workspace per purpose
 enum Slot { W_T = 0, SLAB, BSLAB, STAT_SLAB, STAT_SUMS, STAT_PART, LOSS_WS, LOSS_OUT, TICKETS, HPART, HTICKETS, GN_AFF,
-            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, LN_WS, NSLOTS };
+            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, LN_WS, GNORM_PART, GNORM_TICKET, NSLOTS };
 void* scratch(Slot s, size_t bytes) {
   static void* p[NSLOTS] = {};
   static size_t n[NSLOTS] = {};
@@ -1247,6 +1247,38 @@ void adam_dev(float* p, const float* g, float* m, float* v, void* shadow, long n
 
 void sgd(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum) {
   sgd_step(p, g, vel, static_cast<bf16*>(shadow), n, lr, momentum, nullptr, cur());
+}
+
+void grad_norm_workspace(long n) {
+  scratch(GNORM_PART, (size_t)grad_sumsq_blocks(n) * 4);
+  static bool zeroed = false;  // zeroed once; every launch leaves the ticket zeroed
+  void* t = scratch(GNORM_TICKET, 64 * 4);
+  if (!zeroed) {
+    HOST_HIP_CHECK(hipMemsetAsync(t, 0, 64 * 4, cur()));
+    zeroed = true;
+  }
+}
+
+void grad_sumsq(const float* g, long n, float max_norm, float* out) {
+  if (!gpu::Graph::capturing()) grad_norm_workspace(n);  // (a capture finds what the warm-up steps created)
+  dcnn::grad_sumsq(g, n, max_norm, static_cast<float*>(scratch(GNORM_PART, 0)),
+                   static_cast<unsigned*>(scratch(GNORM_TICKET, 0)), out, cur());
+}
+
+void adam_tail(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
+               float eps, float bc1, float bc2, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay,
+               const float* coef, float* ema, float decay) {
+  adam_step_tail(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, hyper,
+                 nodecay, coef, ema, decay, cur());
+}
+
+void sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum, const float* coef,
+              float* ema, float decay) {
+  sgd_step_tail(p, g, vel, static_cast<bf16*>(shadow), n, lr, momentum, nullptr, coef, ema, decay, cur());
+}
+
+void ema_swap(float* a, float* b, void* shadow, long n) {
+  dcnn::ema_swap(a, b, static_cast<bf16*>(shadow), n, cur());
 }
 
 }  // namespace gpu_ops

@@ -171,6 +171,12 @@ std::unique_ptr<Optimizer> create_optimizer(const json::Value& cfg) {
   for (auto& ch : type) ch = (char)std::tolower((unsigned char)ch);
   const json::Value* pp = cfg.find("parameters");
   const json::Value p = pp != nullptr ? *pp : json::Value::object();
+  // a stage's gradient norm is not the model's norm, and the flat optimizer-state transfer does not
+  // carry an EMA buffer: a stage refuses both switches instead of ignoring them
+  for (const char* key : {"max_grad_norm", "ema_decay"})
+    if (p.get_number(key, 0.0) != 0.0)
+      throw std::invalid_argument(std::string("pipeline stage: optimizer option ") + key + "=" +
+                                  std::to_string(p.get_number(key, 0.0)) + " is not supported on a pipeline stage");
   const float lr = (float)p.get_number("learning_rate", type == "sgd" ? 0.01 : 0.001);
   if (type == "sgd") return std::make_unique<SGD>(lr, (float)p.get_number("momentum", 0.0));
   if (type == "adam" || type == "adamw") {

@@ -61,6 +61,9 @@ void TrainGraph::capture(const Tensor& x, const Tensor& labels) {
   // BatchNorm running statistics)
   const Tensor v0 = a->value.clone(), m0 = a->m.clone(), w0 = a->v.clone(), s0 = a->shadow.clone();
   std::vector<std::pair<Tensor, Tensor>> bn0;  // (live buffer, its snapshot)
+  // (and the weight EMA, created now when it is on: the warm-up steps must not average)
+  opt_.prepare(params);
+  if (a->ema.defined()) bn0.emplace_back(a->ema, a->ema.clone());
   for (BatchNorm* bn : model_.batchnorms())
     for (Tensor* t : {&bn->running_mean, &bn->running_var})
       if (t->defined()) bn0.emplace_back(*t, t->clone());

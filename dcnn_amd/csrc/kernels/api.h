@@ -390,6 +390,22 @@ void adam_step_nodecay(float* p, const float* g, float* m, float* v, bf16* shado
 void sgd_step(float* p, const float* g, float* vel, bf16* shadow, long n, float lr, float mom, const float* hyper,
               hipStream_t s);
 void adam_scalars(float* hyper, float b1, float b2, hipStream_t s);
+// Global-norm clipping: one launch sums g^2 over the flat gradient in a fixed order (a grid that
+// depends on n only; per-workgroup partials in part [grad_sumsq_blocks(n)], a self-resetting ticket
+// word per stream; neither is needed when one workgroup covers n) and writes out[4] = {sumsq, norm,
+// coef = min(1, max_norm / (norm + 1e-6)), max_norm}. g is 16-byte aligned, any n >= 1.
+int grad_sumsq_blocks(long n);
+void grad_sumsq(const float* g, long n, float max_norm, float* part, unsigned* ticket, float* out, hipStream_t s);
+// The optimizer step with optional inputs (null = off): nodecay (adam_step_nodecay's table), coef
+// (device pointer, the step takes g * coef and leaves g as it is), ema (ema = decay ema + (1 - decay)
+// p_new, decay in (0, 1)). Launched only when clip or EMA is on.
+void adam_step_tail(float* p, const float* g, float* m, float* v, bf16* shadow, long n, float lr, float b1, float b2,
+                    float eps, float bc1, float bc2, float wd, int decoupled, const float* hyper,
+                    const uint8_t* nodecay, const float* coef, float* ema, float decay, hipStream_t s);
+void sgd_step_tail(float* p, const float* g, float* vel, bf16* shadow, long n, float lr, float mom, const float* hyper,
+                   const float* coef, float* ema, float decay, hipStream_t s);
+// exchange the flat fp32 buffers a and b, shadow (optional) = bf16 of the new a; twice restores every bit
+void ema_swap(float* a, float* b, bf16* shadow, long n, hipStream_t s);
 // data-parallel bf16 gradient wire format (comm.hip)
 void grad_pack_bf16(const float* g, bf16* out, long n, float scale, hipStream_t s);
 void grad_sum_chunks_bf16(const bf16* src, int w, long ld, long n, bf16* dst, hipStream_t s);

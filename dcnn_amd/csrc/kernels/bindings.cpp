@@ -670,6 +670,27 @@ PYBIND11_MODULE(_kernels, m) {
     sgd_step(P<float*>(p), P<const float*>(g), P<float*>(vel), P<bf16*>(shadow), n, lr, mom, P<const float*>(hyper),
              S(st));
   });
+  // global-norm clipping and weight EMA (loss_optim.hip)
+  m.def("grad_sumsq_blocks", &grad_sumsq_blocks);
+  m.def("grad_sumsq", [](uintptr_t g, long n, float max_norm, uintptr_t part, uintptr_t ticket, uintptr_t out,
+                         uintptr_t st) {
+    grad_sumsq(P<const float*>(g), n, max_norm, P<float*>(part), P<unsigned*>(ticket), P<float*>(out), S(st));
+  });
+  m.def("adam_step_tail", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t shadow, long n, float lr,
+                             float b1, float b2, float eps, float bc1, float bc2, float wd, int dec, uintptr_t hyper,
+                             uintptr_t nodecay, uintptr_t coef, uintptr_t ema, float decay, uintptr_t st) {
+    adam_step_tail(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(shadow), n, lr, b1, b2, eps,
+                   bc1, bc2, wd, dec, P<const float*>(hyper), P<const uint8_t*>(nodecay), P<const float*>(coef),
+                   P<float*>(ema), decay, S(st));
+  });
+  m.def("sgd_step_tail", [](uintptr_t p, uintptr_t g, uintptr_t vel, uintptr_t shadow, long n, float lr, float mom,
+                            uintptr_t hyper, uintptr_t coef, uintptr_t ema, float decay, uintptr_t st) {
+    sgd_step_tail(P<float*>(p), P<const float*>(g), P<float*>(vel), P<bf16*>(shadow), n, lr, mom,
+                  P<const float*>(hyper), P<const float*>(coef), P<float*>(ema), decay, S(st));
+  });
+  m.def("ema_swap", [](uintptr_t a, uintptr_t b, uintptr_t shadow, long n, uintptr_t st) {
+    ema_swap(P<float*>(a), P<float*>(b), P<bf16*>(shadow), n, S(st));
+  });
   m.def("zero_bytes", [](uintptr_t p, long nbytes, uintptr_t st) { zero_bytes(P<void*>(p), nbytes, S(st)); });
   m.def("grad_pack_bf16", [](uintptr_t g, uintptr_t out, long n, float scale, uintptr_t st) {
     grad_pack_bf16(P<const float*>(g), P<bf16*>(out), n, scale, S(st));

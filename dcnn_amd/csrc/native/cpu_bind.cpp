@@ -210,6 +210,27 @@ void bind_cpu(py::module_& parent) {
     DT_DISPATCH(dt, adam_step_nodecay<T>(P<T>(p), P<const T>(g), P<T>(mm), P<T>(v), n, lr, b1, b2, eps, bc1, bc2, wd,
                                          dec, P<const uint8_t>(nodecay)));
   }, Rel());
+  // global-norm clipping / weight EMA: the sum of g^2, the steps with their optional inputs (a null
+  // pointer or clip = false switches one off), the weight <-> EMA exchange
+  m.def("grad_sumsq", [](int dt, uintptr_t g, long n) {
+    double r = 0;
+    DT_DISPATCH(dt, r = grad_sumsq<T>(P<const T>(g), n));
+    return r;
+  }, Rel());
+  m.def("adam_step_tail", [](int dt, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, long n, double lr, double b1,
+                             double b2, double eps, double bc1, double bc2, double wd, int dec, uintptr_t nodecay,
+                             bool clip, double coef, uintptr_t ema, double decay) {
+    DT_DISPATCH(dt, adam_step_tail<T>(P<T>(p), P<const T>(g), P<T>(mm), P<T>(v), n, lr, b1, b2, eps, bc1, bc2, wd, dec,
+                                      P<const uint8_t>(nodecay), clip ? &coef : nullptr, P<T>(ema), decay));
+  }, Rel());
+  m.def("sgd_step_tail", [](int dt, uintptr_t p, uintptr_t g, uintptr_t vel, long n, double lr, double mom, bool clip,
+                            double coef, uintptr_t ema, double decay) {
+    DT_DISPATCH(dt, sgd_step_tail<T>(P<T>(p), P<const T>(g), P<T>(vel), n, lr, mom, clip ? &coef : nullptr, P<T>(ema),
+                                     decay));
+  }, Rel());
+  m.def("ema_swap", [](int dt, uintptr_t a, uintptr_t b, long n) {
+    DT_DISPATCH(dt, ema_swap<T>(P<T>(a), P<T>(b), n));
+  }, Rel());
   // the N mask values of stochastic depth for (seed, draw), as a list
   m.def("drop_path_mask", [](uint64_t seed, uint64_t draw, long N, double p) {
     if (N < 1) throw std::invalid_argument("drop_path_mask: N < 1");

@@ -100,6 +100,18 @@ void adam_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, doubl
 template <typename T>
 void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
                        double bc2, double wd, int decoupled, const uint8_t* nodecay);
+// Global-norm clipping and weight EMA. grad_sumsq: sum of g^2 in a fixed order (double partials).
+// The tail steps are adam_step / sgd_step with optional inputs, null = off: nodecay (as above), coef
+// (the step takes g * coef, g is left as it is), ema (ema = decay ema + (1 - decay) p_new).
+template <typename T> double grad_sumsq(const T* g, long n);
+template <typename T>
+void adam_step_tail(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+                    double bc2, double wd, int decoupled, const uint8_t* nodecay, const double* coef, T* ema,
+                    double decay);
+template <typename T>
+void sgd_step_tail(T* p, const T* g, T* vel, long n, double lr, double momentum, const double* coef, T* ema,
+                   double decay);
+template <typename T> void ema_swap(T* a, T* b, long n);
 // stochastic depth: mask[n] = 0 or 1 / (1 - p), the GPU's mask (csrc/kernels/droppath.hip) bit for
 // bit; y[n][:] = mask[n] x[n][:] over samples of `row` contiguous elements
 void drop_path_mask(float* mask, long N, double p, uint64_t seed, uint64_t draw);

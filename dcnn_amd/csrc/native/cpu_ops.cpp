@@ -1504,6 +1504,69 @@ void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b
   });
 }
 
+// ------------------------------------------------------------------ gradient clipping / weight EMA
+// Sum of g^2 over the flat gradient (fixed chunking, partials in double, summed in order).
+template <typename T>
+double grad_sumsq(const T* g, long n) {
+  return det_sum(n, [&](long i) {
+    const double x = g[i];
+    return x * x;
+  });
+}
+
+// adam_step with three optional inputs (null = off): nodecay (adam_step_nodecay's block table), coef
+// (the clip coefficient: the step takes g * coef and leaves g as it is) and ema
+// (ema = decay ema + (1 - decay) p_new).
+template <typename T>
+void adam_step_tail(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+                    double bc2, double wd, int decoupled, const uint8_t* nodecay, const double* coef, T* ema,
+                    double decay) {
+  const double c = coef ? *coef : 1.0;
+  for_chunks(n, kGrain, [&](long lo, long hi) {
+    for (long i = lo; i < hi; ++i) {
+      const double w = nodecay && nodecay[i >> 6] ? 0.0 : wd;
+      const double gi = coef ? g[i] * c : (double)g[i];
+      m[i] = (T)(b1 * m[i] + (1.0 - b1) * gi);
+      v[i] = (T)(b2 * v[i] + (1.0 - b2) * gi * gi);
+      double upd = lr * (m[i] / bc1) / (std::sqrt(v[i] / bc2) + eps);
+      if (w > 0) {
+        if (decoupled)
+          p[i] -= (T)(w * lr * p[i]);
+        else
+          upd += w * lr * p[i];
+      }
+      p[i] -= (T)upd;
+      if (ema) ema[i] = (T)(decay * ema[i] + (1.0 - decay) * p[i]);
+    }
+  });
+}
+
+template <typename T>
+void sgd_step_tail(T* p, const T* g, T* vel, long n, double lr, double momentum, const double* coef, T* ema,
+                   double decay) {
+  const double c = coef ? *coef : 1.0;
+  for_chunks(n, kGrain, [&](long lo, long hi) {
+    for (long i = lo; i < hi; ++i) {
+      const double gi = coef ? g[i] * c : (double)g[i];
+      if (vel) {
+        vel[i] = (T)(momentum * vel[i] - lr * gi);
+        p[i] += vel[i];
+      } else {
+        p[i] -= (T)(lr * gi);
+      }
+      if (ema) ema[i] = (T)(decay * ema[i] + (1.0 - decay) * p[i]);
+    }
+  });
+}
+
+// exchange two flat buffers (a model's weights and their EMA); twice restores every bit
+template <typename T>
+void ema_swap(T* a, T* b, long n) {
+  for_chunks(n, kGrain, [&](long lo, long hi) {
+    for (long i = lo; i < hi; ++i) std::swap(a[i], b[i]);
+  });
+}
+
 // ------------------------------------------------------------------ instantiations
 #define DCNN_CPU_INST(T)                                                                                             \
   template void elementwise<T>(int, int, const T*, const T*, T*, long, double, double);                             \
@@ -1553,7 +1616,12 @@ void adam_step_nodecay(T* p, const T* g, T* m, T* v, long n, double lr, double b
   template void adam_step<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double, int); \
   template void drop_path_scale<T>(const T*, const float*, T*, long, long);                                          \
   template void adam_step_nodecay<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double,     \
-                                     double, int, const uint8_t*);
+                                     double, int, const uint8_t*);                                                   \
+  template double grad_sumsq<T>(const T*, long);                                                                     \
+  template void adam_step_tail<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double, \
+                                  int, const uint8_t*, const double*, T*, double);                                   \
+  template void sgd_step_tail<T>(T*, const T*, T*, long, double, double, const double*, T*, double);                 \
+  template void ema_swap<T>(T*, T*, long);
 
 DCNN_CPU_INST(float)
 DCNN_CPU_INST(double)

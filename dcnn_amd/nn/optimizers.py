@@ -8,9 +8,27 @@ corrections advance ON THE DEVICE (``adam_scalars``, captured in the step graph 
 update), and the learning rate is uploaded only when it changes — a replayed training step needs
 no host-to-device transfer besides its input batch. A CPU arena is updated by the native
 backend's flat-buffer loops (``ops/cpu.py``), in the arena's dtype (float32 or float64).
+
+Every optimizer takes two switches that belong to the step, both off by default:
+
+``max_grad_norm > 0``: global-norm gradient clipping (torch's ``clip_grad_norm_``, L2). One
+deterministic reduction over the flat gradient leaves ``{sumsq, norm, coef, max_norm}`` with
+``coef = min(1, max_grad_norm / (norm + 1e-6))`` in device memory (``opt.grad_norm_device``) and the
+step takes ``g * coef``: no host read, so a captured step stays one graph. The gradient buffers are
+NOT rewritten: ``model.gradients()`` still shows the unclipped gradient. A non-finite norm propagates
+into the step as it does in torch; no step is skipped. Under data parallelism the norm is taken when
+the step is launched, behind the all-reduce: it is the norm of the averaged gradient.
+
+``ema_decay`` in (0, 1): an exponential moving average of the weights, ``opt.ema`` (a flat fp32
+buffer of the arena's size, a copy of the weights at ``attach``), updated inside the step kernel:
+``ema = d ema + (1 - d) p_new`` with a fixed decay (no warm-up of the decay). BatchNorm running
+statistics are not averaged: evaluating inside ``opt.ema_weights()`` uses the live statistics.
+
+With both off a step launches exactly what it launched before they existed.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List, Optional
 
@@ -46,9 +64,34 @@ def _arena_of(params: List[torch.Tensor]):
     return base
 
 
+def _check_tail(max_grad_norm, ema_decay):
+    mg, ed = float(max_grad_norm), float(ema_decay)
+    if not mg >= 0.0 or math.isinf(mg):
+        raise ValueError(f"max_grad_norm {max_grad_norm!r} is not a finite value >= 0 (0 switches clipping off)")
+    if not 0.0 <= ed < 1.0:
+        raise ValueError(f"ema_decay {ema_decay!r} is not in [0, 1) (0 switches the weight EMA off)")
+    return mg, ed
+
+
+def refuse_tail_options(config, who: str) -> None:
+    """Raise for an optimizer config with clipping or the weight EMA on, where they cannot be honoured
+    (a pipeline stage: its norm is not the model's norm, and the flat optimizer-state transfer does not
+    know the EMA buffer)."""
+    params = (config or {}).get("parameters", {}) if isinstance(config, dict) else {}
+    for key in ("max_grad_norm", "ema_decay"):
+        if float(params.get(key, 0.0) or 0.0) != 0.0:
+            raise ValueError(f"{who}: optimizer option {key}={params[key]!r} is not supported on a pipeline "
+                             f"stage (a per-stage gradient norm is not the model's norm, and the stage's "
+                             f"optimizer-state transfer does not carry an EMA buffer)")
+
+
 class Optimizer:
-    def __init__(self, learning_rate: float):
+    def __init__(self, learning_rate: float, max_grad_norm: float = 0.0, ema_decay: float = 0.0):
         self.learning_rate = float(learning_rate)
+        self.max_grad_norm, self.ema_decay = _check_tail(max_grad_norm, ema_decay)
+        self.ema: Optional[List[torch.Tensor]] = None  # [flat buffer] on an arena, else one per parameter
+        self.grad_norm_device: Optional[torch.Tensor] = None  # {sumsq, norm, coef, max_norm}
+        self._model = None
         self.params: List[torch.Tensor] = []
         self.grads: List[torch.Tensor] = []
         self.arena = None
@@ -61,8 +104,9 @@ class Optimizer:
         """``no_decay``: one bool per parameter, True for those excluded from weight decay (biases,
         norm affines, layer scales — each layer classes its own, ``ParamSpec.no_decay``). Taken
         from the model or the arena when one is given."""
+        self._model = None
         if grads is None and hasattr(params, "parameters"):
-            model = params
+            model = self._model = params
             params, grads = model.parameters(), model.gradients()
             arena = getattr(model, "arena", None)
             if no_decay is None and hasattr(model, "no_decay_flags"):
@@ -87,9 +131,106 @@ class Optimizer:
         # learning rate) must be re-uploaded too, or the device keeps counting from the old t
         self._hyper_dirty = True
         self._on_attach()
+        self._attach_tail()
 
     def _on_attach(self):
         pass
+
+    # ------------------------------------------------------------ gradient clipping / weight EMA
+    def _tail(self) -> bool:
+        return self.max_grad_norm > 0.0 or self.ema_decay > 0.0
+
+    def _attach_tail(self):
+        self.ema = self.grad_norm_device = None
+        if not self.params:
+            return
+        if self.ema_decay > 0.0:
+            if self.arena is not None:
+                self.ema = [self.arena.new_zeros()]
+                self.ema[0].copy_(self.arena.data)
+            else:
+                self.ema = [p.detach().clone() for p in self.params]
+        if self.max_grad_norm > 0.0:
+            ref = self._flat_p if self.arena is not None else self.params[0]
+            self.grad_norm_device = torch.zeros(4, dtype=ref.dtype, device=ref.device)
+            self.grad_norm_device[2] = 1.0
+            self.grad_norm_device[3] = self.max_grad_norm
+
+    def _launch_norm(self):
+        """GPU arena: the norm of the gradient the step is about to consume, left on the device."""
+        if self.max_grad_norm > 0.0:
+            from ..ops import hip
+            hip.grad_sumsq(self._flat_g, self.max_grad_norm, self.grad_norm_device)
+            return self.grad_norm_device[2:3]
+        return None
+
+    def _host_coef(self):
+        """CPU paths: the global norm over ALL gradients (not per tensor) and the coefficient, also
+        written to ``grad_norm_device``. None when clipping is off."""
+        if not self.max_grad_norm > 0.0:
+            return None
+        if self.arena is not None:
+            from ..ops import cpu
+            sumsq = cpu.grad_sumsq(self._flat_g)
+        else:
+            sumsq = float(sum(float((g.detach().double() ** 2).sum()) for g in self.grads))
+        norm = math.sqrt(sumsq) if sumsq == sumsq and sumsq >= 0 else float("nan")
+        c = self.max_grad_norm / (norm + 1e-6)
+        coef = c if (c < 1.0 or c != c) else 1.0
+        self.grad_norm_device.copy_(torch.tensor([sumsq, norm, coef, self.max_grad_norm], dtype=torch.float64))
+        return coef
+
+    def _ema_torch(self, i, p):
+        if self.ema is not None:
+            self.ema[i].mul_(self.ema_decay).add_((1.0 - self.ema_decay) * p)
+
+    def last_grad_norm(self) -> Optional[float]:
+        """The gradient norm of the last step (before clipping), read on the host: a device
+        synchronisation, so not for the hot path. None when clipping is off."""
+        return None if self.grad_norm_device is None else float(self.grad_norm_device[1].item())
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body on the EMA weights: the flat master buffer and the EMA buffer are exchanged
+        (one launch, which also refreshes the bf16 shadow), the derived weight operands the model
+        caches are invalidated, and on exit everything is exchanged back bit for bit. Use it
+        between steps only, never inside one. BatchNorm running statistics are not averaged: the
+        body sees the live ones. No-op when the EMA is off."""
+        if self.ema is None:
+            yield
+            return
+        self._swap_ema()
+        try:
+            yield
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self):
+        if self.arena is not None:
+            if self._flat_p.is_cuda:
+                from ..ops import hip
+                hip.ema_swap(self._flat_p, self.ema[0], self.arena.shadow)
+                self.arena.mark_synced()
+            else:
+                from ..ops import cpu
+                cpu.ema_swap(self._flat_p, self.ema[0])
+                self.arena.sync_shadow(force=True)
+        else:
+            with torch.no_grad():
+                for p, e in zip(self.params, self.ema):
+                    t = p.detach().clone()
+                    p.copy_(e)
+                    e.copy_(t)
+        tr = getattr(self._model, "_transposer", None)
+        if tr is not None:
+            tr.invalidate()  # dgrad weight operands: regenerated from the weights by the next step
+
+    def _tail_state(self) -> dict:
+        return {"ema": [e.detach().cpu() for e in self.ema]} if self.ema else {}
+
+    def _load_tail_state(self, d: dict) -> None:
+        for dst, src in zip(self.ema or [], d.get("ema", [])):
+            dst.copy_(src)
 
     def update(self) -> None:
         raise NotImplementedError
@@ -153,8 +294,9 @@ class Optimizer:
 
 
 class SGD(Optimizer):
-    def __init__(self, learning_rate: float = 0.01, momentum: float = 0.0):
-        super().__init__(learning_rate)
+    def __init__(self, learning_rate: float = 0.01, momentum: float = 0.0, max_grad_norm: float = 0.0,
+                 ema_decay: float = 0.0):
+        super().__init__(learning_rate, max_grad_norm, ema_decay)
         self.momentum = float(momentum)
         self.velocity = None
 
@@ -172,8 +314,13 @@ class SGD(Optimizer):
 
     def launch_step(self):
         from ..ops import hip
-        hip.sgd_step(self._flat_p, self._flat_g, self.velocity[0] if self.momentum > 0 else None, self.arena.shadow,
-                     self.learning_rate, self.momentum, self._hyper)
+        vel = self.velocity[0] if self.momentum > 0 else None
+        if self._tail():
+            hip.sgd_step_tail(self._flat_p, self._flat_g, vel, self.arena.shadow, self.learning_rate, self.momentum,
+                              self._hyper, self._launch_norm(), self.ema[0] if self.ema else None, self.ema_decay)
+        else:
+            hip.sgd_step(self._flat_p, self._flat_g, vel, self.arena.shadow, self.learning_rate, self.momentum,
+                         self._hyper)
         self.arena.mark_synced()
 
     def fused(self) -> bool:
@@ -187,11 +334,19 @@ class SGD(Optimizer):
                 self.launch_step()
                 return
             from ..ops import cpu
-            cpu.sgd_step(p, g, self.velocity[0] if self.momentum > 0 else None, self.learning_rate, self.momentum)
+            vel = self.velocity[0] if self.momentum > 0 else None
+            if self._tail():
+                cpu.sgd_step_tail(p, g, vel, self.learning_rate, self.momentum, self._host_coef(),
+                                  self.ema[0] if self.ema else None, self.ema_decay)
+            else:
+                cpu.sgd_step(p, g, vel, self.learning_rate, self.momentum)
             self.arena.sync_shadow()
             return
+        coef = self._host_coef()  # over all parameters, before any of them is stepped
         for i, (p, g) in enumerate(zip(self.params, self.grads)):
-            self._sgd_torch(p, g, self.velocity[i] if self.momentum > 0 else None)
+            self._sgd_torch(p, g if coef is None else g * coef, self.velocity[i] if self.momentum > 0 else None)
+            with torch.no_grad():
+                self._ema_torch(i, p)
 
     def _sgd_torch(self, p, g, v):
         with torch.no_grad():
@@ -205,15 +360,17 @@ class SGD(Optimizer):
         return "SGD"
 
     def get_config(self):
-        return OptimizerConfig("sgd", "SGD", {"learning_rate": self.learning_rate, "momentum": self.momentum})
+        return OptimizerConfig("sgd", "SGD", {"learning_rate": self.learning_rate, "momentum": self.momentum,
+                                              "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay})
 
     def clone(self):
-        return SGD(self.learning_rate, self.momentum)
+        return SGD(self.learning_rate, self.momentum, self.max_grad_norm, self.ema_decay)
 
     def state_dict(self):
-        return {"velocity": [v.detach().cpu() for v in self.velocity] if self.velocity else []}
+        return {"velocity": [v.detach().cpu() for v in self.velocity] if self.velocity else [], **self._tail_state()}
 
     def load_state_dict(self, d):
+        self._load_tail_state(d)
         if d.get("velocity") and self.velocity:
             for v, s in zip(self.velocity, d["velocity"]):
                 v.copy_(s)
@@ -222,11 +379,14 @@ class SGD(Optimizer):
 class Adam(Optimizer):
     def __init__(self, learning_rate: float = 0.001, beta1: float = 0.9, beta2: float = 0.999,
                  epsilon: float = 1e-8, weight_decay: float = 0.0, decouple_weight_decay: bool = False,
-                 no_decay_norm_bias: bool = False):
+                 no_decay_norm_bias: bool = False, max_grad_norm: float = 0.0, ema_decay: float = 0.0):
         """``no_decay_norm_bias``: biases, norm affines and layer scales take the step without
         weight decay. On the fused arena path a static device table of one byte per 64-element
-        block selects them inside the one launch; off (the default), the launch is unchanged."""
-        super().__init__(learning_rate)
+        block selects them inside the one launch; off (the default), the launch is unchanged.
+        ``max_grad_norm`` / ``ema_decay``: global-norm clipping and the weight EMA (module docstring);
+        with either on, the step is the norm reduction plus one instance of the step kernel that
+        reads the coefficient and maintains the EMA."""
+        super().__init__(learning_rate, max_grad_norm, ema_decay)
         self.no_decay_norm_bias = bool(no_decay_norm_bias)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
         self.weight_decay = float(weight_decay)
@@ -271,9 +431,13 @@ class Adam(Optimizer):
         kernels().adam_scalars(self._hyper.data_ptr(), float(self.beta1), float(self.beta2),
                                stream_ptr(self._flat_p.device))
         bc1, bc2 = self._bc
-        hip.adam_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate,
-                      self.beta1, self.beta2, self.epsilon, bc1, bc2, self.weight_decay,
-                      self.decouple_weight_decay, self._hyper, nodecay=self._nodecay_blocks)
+        args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate, self.beta1,
+                self.beta2, self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay, self._hyper)
+        if self._tail():
+            hip.adam_step_tail(*args, nodecay=self._nodecay_blocks, coef=self._launch_norm(),
+                               ema=self.ema[0] if self.ema else None, ema_decay=self.ema_decay)
+        else:
+            hip.adam_step(*args, nodecay=self._nodecay_blocks)
         self.arena.mark_synced()
 
     def update(self):
@@ -288,16 +452,22 @@ class Adam(Optimizer):
             from ..ops import cpu   # native flat-buffer step (CPU arena, float32 or float64)
             args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1, self.beta2,
                     self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay)
-            if self._nodecay_blocks is not None:
+            if self._tail():
+                cpu.adam_step_tail(*args, self._nodecay_blocks, self._host_coef(), self.ema[0] if self.ema else None,
+                                   self.ema_decay)
+            elif self._nodecay_blocks is not None:
                 cpu.adam_step_nodecay(*args, self._nodecay_blocks)
             else:
                 cpu.adam_step(*args)
             self.arena.sync_shadow()
             return
         pairs = [(self._flat_p, self._flat_g)] if self.arena is not None else list(zip(self.params, self.grads))
+        coef = self._host_coef()  # over all parameters, before any of them is stepped
         with torch.no_grad():
             for i, (p, g) in enumerate(pairs):
                 m, v = self.m[i], self.v[i]
+                if coef is not None:
+                    g = g * coef
                 m.mul_(self.beta1).add_((1 - self.beta1) * g)
                 v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
                 upd = self.learning_rate * (m / bc1) / (torch.sqrt(v / bc2) + self.epsilon)
@@ -308,6 +478,7 @@ class Adam(Optimizer):
                     else:
                         upd = upd + wd * self.learning_rate * p
                 p.sub_(upd)
+                self._ema_torch(i, p)
         if self.arena is not None:
             self.arena.sync_shadow()
 
@@ -320,16 +491,19 @@ class Adam(Optimizer):
                                                     beta2=self.beta2, epsilon=self.epsilon,
                                                     weight_decay=self.weight_decay,
                                                     decouple_weight_decay=self.decouple_weight_decay,
-                                                    no_decay_norm_bias=self.no_decay_norm_bias))
+                                                    no_decay_norm_bias=self.no_decay_norm_bias,
+                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
 
     def clone(self):
         return Adam(self.learning_rate, self.beta1, self.beta2, self.epsilon, self.weight_decay,
-                    self.decouple_weight_decay, self.no_decay_norm_bias)
+                    self.decouple_weight_decay, self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
 
     def state_dict(self):
-        return {"t": self.t, "m": [x.detach().cpu() for x in self.m or []], "v": [x.detach().cpu() for x in self.v or []]}
+        return {"t": self.t, "m": [x.detach().cpu() for x in self.m or []], "v": [x.detach().cpu() for x in self.v or []],
+                **self._tail_state()}
 
     def load_state_dict(self, d):
+        self._load_tail_state(d)
         self.t = int(d.get("t", 0))
         self._hyper_dirty = True
         for dst, src in zip(self.m or [], d.get("m", [])):
@@ -340,8 +514,9 @@ class Adam(Optimizer):
 
 class AdamW(Adam):
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=0.01,
-                 no_decay_norm_bias=False):
-        super().__init__(learning_rate, beta1, beta2, epsilon, weight_decay, True, no_decay_norm_bias)
+                 no_decay_norm_bias=False, max_grad_norm=0.0, ema_decay=0.0):
+        super().__init__(learning_rate, beta1, beta2, epsilon, weight_decay, True, no_decay_norm_bias, max_grad_norm,
+                         ema_decay)
 
 
 class OptimizerFactory:
@@ -352,9 +527,11 @@ class OptimizerFactory:
         t = config["type"]
         p = config["parameters"]
         if t == "sgd":
-            return SGD(p.get("learning_rate", 0.01), p.get("momentum", 0.0))
+            return SGD(p.get("learning_rate", 0.01), p.get("momentum", 0.0), p.get("max_grad_norm", 0.0),
+                       p.get("ema_decay", 0.0))
         if t in ("adam", "adamw"):
             return Adam(p.get("learning_rate", 0.001), p.get("beta1", 0.9), p.get("beta2", 0.999),
                         p.get("epsilon", 1e-8), p.get("weight_decay", 0.0),
-                        p.get("decouple_weight_decay", t == "adamw"), p.get("no_decay_norm_bias", False))
+                        p.get("decouple_weight_decay", t == "adamw"), p.get("no_decay_norm_bias", False),
+                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
         raise ValueError(f"Unknown optimizer type: {t}")

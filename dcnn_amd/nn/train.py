@@ -57,6 +57,8 @@ class TrainingConfig:
     mix_prob: float = 1.0
     mix_switch_prob: float = 0.5
     label_smoothing: float = 0.0    # of the soft_crossentropy loss (examples build the loss from it)
+    max_grad_norm: float = 0.0      # global-norm gradient clipping of the optimizer step (0 = off)
+    ema_decay: float = 0.0          # weight EMA kept by the optimizer; validation then runs on the EMA weights
 
     def load_from_env(self) -> "TrainingConfig":
         self.epochs = get_env("EPOCHS", DEFAULT_EPOCH)
@@ -75,6 +77,8 @@ class TrainingConfig:
         self.mix_prob = get_env("MIX_PROB", 1.0)
         self.mix_switch_prob = get_env("MIX_SWITCH_PROB", 0.5)
         self.label_smoothing = get_env("LABEL_SMOOTHING", 0.0)
+        self.max_grad_norm = get_env("MAX_GRAD_NORM", 0.0)
+        self.ema_decay = get_env("EMA_DECAY", 0.0)
         return self
 
     def print_config(self) -> None:
@@ -126,6 +130,17 @@ def build_mixer(config: "TrainingConfig", num_classes: int, seed: int = 0):
     from ..data.mix import BatchMixer
     return BatchMixer(num_classes, config.mixup_alpha, config.cutmix_alpha, config.mix_prob, config.mix_switch_prob,
                       seed)
+
+
+def apply_step_options(optimizer, config: "TrainingConfig") -> None:
+    """Hand ``config.max_grad_norm`` / ``config.ema_decay`` to an optimizer that does not set them
+    itself (before ``attach``, which allocates the EMA buffer). Values out of range raise."""
+    from .optimizers import _check_tail
+    mg, ed = _check_tail(config.max_grad_norm, config.ema_decay)
+    if mg > 0.0 and optimizer.max_grad_norm == 0.0:
+        optimizer.max_grad_norm = mg
+    if ed > 0.0 and optimizer.ema_decay == 0.0:
+        optimizer.ema_decay = ed
 
 
 def train_class_epoch(model, train_loader, optimizer, loss_function, config: Optional[TrainingConfig] = None,
@@ -260,6 +275,7 @@ def train_classification_model(model, train_loader, test_loader, optimizer, loss
             train_loader.set_mixer(mixer)
             host_mixer = None
     dp = data_parallel or DataParallel(model, bucket_mb=config.bucket_mb)
+    apply_step_options(optimizer, config)
     optimizer.attach(model)
     train_loader.prepare_batches(config.batch_size)
     test_loader.prepare_batches(config.batch_size)
@@ -282,7 +298,10 @@ def train_classification_model(model, train_loader, test_loader, optimizer, loss
             torch.cuda.synchronize()
         train_ms = (time.perf_counter() - t0) * 1e3
         dp.sync_batchnorm_buffers()
-        va_loss, va_acc = validate_class_model(model, test_loader, loss_function, config.max_batches_per_epoch)
+        # with a weight EMA the validated model is the averaged one (BatchNorm running statistics are
+        # not averaged: the live ones are used); a no-op context when the EMA is off
+        with optimizer.ema_weights():
+            va_loss, va_acc = validate_class_model(model, test_loader, loss_function, config.max_batches_per_epoch)
         n_img = train_loader.size() if not config.max_batches_per_epoch else \
             min(train_loader.size(), config.max_batches_per_epoch * config.batch_size)
         rec = {"epoch": epoch + 1, "train_loss": tr_loss, "train_acc": tr_acc, "val_loss": va_loss, "val_acc": va_acc,

@@ -506,6 +506,47 @@ def adam_step_nodecay(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, decoupled, nod
                           nodecay.data_ptr())
 
 
+def grad_sumsq(g) -> float:
+    """Sum of ``g**2`` over a flat float32 / float64 buffer, in a fixed order (double partials)."""
+    g = _c(g)
+    return float(C().grad_sumsq(dt(g), g.data_ptr(), g.numel()))
+
+
+def _nodecay_ptr(who, nodecay, n):
+    if nodecay is None:
+        return 0
+    if nodecay.dtype != torch.uint8 or not nodecay.is_contiguous() or nodecay.numel() * 64 < n:
+        raise ValueError(f"{who}: the block table is uint8 with one entry per 64 elements")
+    return nodecay.data_ptr()
+
+
+def adam_step_tail(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, decoupled, nodecay=None, coef=None, ema=None,
+                   ema_decay=0.0):
+    """:func:`adam_step` with three optional inputs: ``nodecay`` (the block table of
+    :func:`adam_step_nodecay`), ``coef`` (the clip coefficient: the step takes ``g * coef``, ``g`` is
+    left as it is) and ``ema`` (``ema = d ema + (1 - d) p_new``)."""
+    _same(p_, g, m, v, ema)
+    C().adam_step_tail(dt(p_), p_.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p_.numel(), float(lr),
+                       float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled),
+                       _nodecay_ptr("adam_step_tail", nodecay, p_.numel()), coef is not None,
+                       float(coef if coef is not None else 1.0), p(ema), float(ema_decay))
+
+
+def sgd_step_tail(p_, g, vel, lr, momentum, coef=None, ema=None, ema_decay=0.0):
+    """:func:`sgd_step` with the clip coefficient and the EMA buffer, both optional."""
+    _same(p_, g, vel, ema)
+    C().sgd_step_tail(dt(p_), p_.data_ptr(), g.data_ptr(), p(vel), p_.numel(), float(lr), float(momentum),
+                      coef is not None, float(coef if coef is not None else 1.0), p(ema), float(ema_decay))
+
+
+def ema_swap(a, b):
+    """Exchange two flat buffers of one dtype and size in place; twice restores every bit."""
+    _same(a, b)
+    if a.numel() != b.numel() or not a.is_contiguous() or not b.is_contiguous() or a.data_ptr() == b.data_ptr():
+        raise ValueError("ema_swap: two distinct contiguous buffers of one size")
+    C().ema_swap(dt(a), a.data_ptr(), b.data_ptr(), a.numel())
+
+
 def mix_plan(seed: int, step: int, H: int, W: int, mixup_alpha: float, cutmix_alpha: float, prob: float = 1.0,
              switch_prob: float = 0.5):
     """The Mixup / CutMix draw of training batch ``step`` (from 1): ``(mode, lam, yl, yh, xl, xh)``,

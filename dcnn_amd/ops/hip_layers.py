@@ -354,6 +354,57 @@ def sgd_step(p, g, vel, shadow, lr, momentum, hyper=None):
                        ptr(hyper), stream_ptr())
 
 
+def _flat_f32(who, *ts):
+    n = ts[0].numel()
+    for t in ts:
+        if t is not None and (t.dtype != F32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
+            raise ValueError(f"{who}: flat contiguous float32 GPU buffers of one size")
+    return n
+
+
+def grad_sumsq(g, max_norm, out):
+    """``out[4] = {sum g^2, norm, coef, max_norm}`` with ``coef = min(1, max_norm / (norm + 1e-6))``:
+    one launch on the current stream, a fixed summation order (bit-reproducible, eager or replayed),
+    no host sync. ``out`` is a 4-float device tensor."""
+    n = _flat_f32("grad_sumsq", g)
+    if out.dtype != F32 or not out.is_cuda or out.numel() < 4 or not out.is_contiguous():
+        raise ValueError("grad_sumsq: out is a float32 GPU tensor of 4 elements")
+    K = kernels()
+    nb = K.grad_sumsq_blocks(n)
+    part = _empty((nb,), F32, g.device) if nb > 1 else None
+    tk = _ticket(g.device, 0, slot="gradnorm") if nb > 1 else None
+    K.grad_sumsq(g.data_ptr(), n, float(max_norm), ptr(part), ptr(tk), out.data_ptr(), stream_ptr(g.device))
+    return out
+
+
+def adam_step_tail(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, wd, decoupled, hyper=None, nodecay=None, coef=None,
+                   ema=None, ema_decay=0.0):
+    """The Adam / AdamW step with its optional inputs: ``nodecay`` (block table), ``coef`` (a device
+    tensor whose first element is the clip coefficient; the step takes ``g * coef``, ``g`` is not
+    rewritten) and ``ema`` (``ema = d ema + (1 - d) p_new``). Launched only when clip or EMA is on."""
+    n = _flat_f32("adam_step_tail", p, g, m, v, ema)
+    if nodecay is not None and (nodecay.dtype != torch.uint8 or not nodecay.is_cuda or nodecay.numel() * 64 < n):
+        raise ValueError("adam_step_tail: nodecay is a uint8 GPU tensor with one entry per 64 elements")
+    kernels().adam_step_tail(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(shadow), n, float(lr),
+                             float(b1), float(b2), float(eps), float(bc1), float(bc2), float(wd), int(decoupled),
+                             ptr(hyper), ptr(nodecay), ptr(coef), ptr(ema), float(ema_decay), stream_ptr(p.device))
+
+
+def sgd_step_tail(p, g, vel, shadow, lr, momentum, hyper=None, coef=None, ema=None, ema_decay=0.0):
+    n = _flat_f32("sgd_step_tail", p, g, vel, ema)
+    kernels().sgd_step_tail(p.data_ptr(), g.data_ptr(), ptr(vel), ptr(shadow), n, float(lr), float(momentum),
+                            ptr(hyper), ptr(coef), ptr(ema), float(ema_decay), stream_ptr(p.device))
+
+
+def ema_swap(a, b, shadow=None):
+    """Exchange two flat fp32 buffers in one launch; ``shadow`` (bf16, optional) is refreshed from the
+    new ``a``. Twice restores every bit."""
+    n = _flat_f32("ema_swap", a, b)
+    if shadow is not None and shadow.numel() != n:
+        raise ValueError("ema_swap: the shadow has the buffers' size")
+    kernels().ema_swap(a.data_ptr(), b.data_ptr(), ptr(shadow), n, stream_ptr(a.device))
+
+
 def zero_(t):
     """Zero a dense GPU tensor on the current stream with the library's own fill kernel (no ATen
     fill on the hot path). Not hipMemsetAsync: captured into a hipGraph, a memset node wrote

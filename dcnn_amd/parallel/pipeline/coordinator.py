@@ -67,6 +67,8 @@ class Coordinator:
                  heartbeat_s: float = 0.0, heartbeat_misses: int = 3):
         self.model = model
         self.optimizer_config = optimizer.get_config() if hasattr(optimizer, "get_config") else dict(optimizer)
+        from ...nn.optimizers import refuse_tail_options
+        refuse_tail_options(self.optimizer_config, "pipeline coordinator")  # (Python and native stages alike)
         self.loss: Loss = LossFactory.create(loss) if isinstance(loss, str) else loss
         self.num_stages = int(num_stages)
         self.num_microbatches = int(num_microbatches)

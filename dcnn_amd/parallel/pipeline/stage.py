@@ -27,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from ...nn.optimizers import OptimizerFactory
+from ...nn.optimizers import OptimizerFactory, refuse_tail_options
 from ...nn.sequential import Sequential, _all_layers
 from ...nn.layers import BatchNorm
 from . import messages as M
@@ -282,6 +282,7 @@ class PipelineStage:
     def _configure(self, text: str) -> None:
         cfg = StageConfig.from_json(text)
         self.cfg = cfg
+        refuse_tail_options(cfg.optimizer_config, f"pipeline stage {cfg.stage_id}")
         model = Sequential.load_from_config(cfg.model_config)
         if cfg.seed is not None:
             model.set_seed(int(cfg.seed))

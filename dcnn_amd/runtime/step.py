@@ -101,7 +101,7 @@ class TrainStep:
         """Tensors a step mutates: fp32 master weights, optimizer moments, BN running stats."""
         from ..parallel.dp import _bn_buffers
         ts = [self.model.arena.data]
-        for name in ("m", "v", "velocity"):
+        for name in ("m", "v", "velocity", "ema"):  # (ema: the warm-up steps must not average)
             ts += list(getattr(self.opt, name, None) or [])
         for l in self.model.layers:
             ts += _bn_buffers(l)
@@ -120,7 +120,9 @@ class TrainStep:
             self._cap_stream = torch.cuda.Stream(device=self.model.device.torch_device)
             self._cap_stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._cap_stream):
-                hip.prewarm_tickets(self.model.device.torch_device)
+                # "gradnorm": the clipping norm's ticket (a slot an optimizer without clipping never uses)
+                slots = ("loss", "gradnorm") if getattr(self.opt, "max_grad_norm", 0.0) > 0.0 else ("loss",)
+                hip.prewarm_tickets(self.model.device.torch_device, slots)
             torch.cuda.current_stream().wait_stream(self._cap_stream)
         return self._cap_stream
 

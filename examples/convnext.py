@@ -3,7 +3,9 @@
 2022): ConvNeXt-pico on CIFAR-10 or, with ``--tiny``, ConvNeXt-T on Tiny-ImageNet-200: crop + flip +
 normalize, AdamW, softmax cross-entropy. ``--mixup A`` / ``--cutmix A`` / ``--label-smoothing E`` turn on the
 rest of the published recipe (0.8 / 1.0 / 0.1): batches are mixed on the device and the loss becomes
-``soft_crossentropy``. ``--steps N`` is a smoke mode: N training steps on
+``soft_crossentropy``; ``--clip-grad N`` clips the global gradient norm inside the optimizer step and
+``--model-ema D`` keeps an exponential moving average of the weights there (validation then runs on the
+averaged weights; BatchNorm statistics, which ConvNeXt does not have, would not be averaged). ``--steps N`` is a smoke mode: N training steps on
 synthetic data and the losses printed. No reference counterpart (the reference has no LayerNorm, GELU
 or depthwise convolution)."""
 import torch
@@ -29,6 +31,10 @@ def _args(ap):
     ap.add_argument("--cutmix", type=float, default=None, help="CutMix alpha (ConvNeXt: 1.0); default CUTMIX_ALPHA or 0")
     ap.add_argument("--label-smoothing", type=float, default=None,
                     help="label smoothing of the loss (ConvNeXt: 0.1); default LABEL_SMOOTHING or 0")
+    ap.add_argument("--clip-grad", type=float, default=None,
+                    help="global-norm gradient clipping at this L2 norm; default MAX_GRAD_NORM or 0 (off)")
+    ap.add_argument("--model-ema", type=float, default=None,
+                    help="decay of the weight EMA (ConvNeXt: 0.9999); default EMA_DECAY or 0 (off)")
 
 
 a, cfg = parse(__doc__, _args)
@@ -38,11 +44,16 @@ if a.cutmix is not None:
     cfg.cutmix_alpha = a.cutmix
 if a.label_smoothing is not None:
     cfg.label_smoothing = a.label_smoothing
+if a.clip_grad is not None:
+    cfg.max_grad_norm = a.clip_grad
+if a.model_ema is not None:
+    cfg.ema_decay = a.model_ema
 soft = cfg.mixup_alpha > 0 or cfg.cutmix_alpha > 0 or cfg.label_smoothing > 0
 kind = "tiny" if a.tiny else "cifar10"
 name = "convnext_tiny_tiny_imagenet" if a.tiny else "convnext_pico_cifar10"
 model = place(create_model(name, drop_path_rate=a.drop_path), a)
-opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05, no_decay_norm_bias=a.no_decay_norm_bias)
+opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05, no_decay_norm_bias=a.no_decay_norm_bias,
+            max_grad_norm=cfg.max_grad_norm, ema_decay=cfg.ema_decay)
 loss_fn = LossFactory.create("soft_crossentropy", label_smoothing=cfg.label_smoothing) if soft else \
     LossFactory.create("softmax_crossentropy")
 if a.steps > 0:
@@ -63,6 +74,14 @@ if a.steps > 0:
         opt.update()
         losses.append(float(loss))
     print(f"{name}: {model.num_parameters()} parameters, batch {n}, losses " + " ".join(f"{v:.4f}" for v in losses))
+    if opt.max_grad_norm > 0:
+        print(f"last gradient norm {opt.last_grad_norm():.4f} (clipped at {opt.max_grad_norm})")
+    if opt.ema is not None:
+        with opt.ema_weights(), torch.no_grad():
+            model.set_training(False)
+            ema_loss, _, _ = loss_fn.loss_and_grad(model.forward(x), y, want_grad=False)
+            model.set_training(True)
+        print(f"loss on the EMA weights {float(ema_loss):.4f}")
     assert all(v == v for v in losses), "non-finite loss"
 else:
     mean, std = STATS[kind]

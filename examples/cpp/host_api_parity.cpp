@@ -17,8 +17,14 @@
 //                                              one stride-2 basic residual block, forward + backward on
 //                                              fixed data; its input gradient and parameter gradients
 //   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph] [--adamw-no-decay]
-//                         [--mix] [--switch-to-labels]
+//                         [--mix] [--switch-to-labels] [--clip-ema MAX_NORM]
 //                                              Adam steps on a synthetic set, then save
+//                                              (--clip-ema: global-norm clipping at MAX_NORM and a
+//                                              weight EMA of decay 0.9; the EMA weights are saved
+//                                              too, as <save>.ema, and the last gradient norm printed;
+//                                              the initial model goes to <save>.init and batch i to
+//                                              <save>.x<i>.bin / <save>.y<i>.bin; with --graph every
+//                                              step runs through TrainGraph, on the CPU as well)
 //   grads / train also take [--drop-path RATE] [--seed-drop-path] (ConvNeXt models)
 // Output is plain text: one "key v0 v1 ..." line per item.
 #include <algorithm>
@@ -356,6 +362,13 @@ int main(int argc, char** argv) {
       const bool nd = flag_arg(argc, argv, "--adamw-no-decay");
       Adam opt(1e-3f, 0.9f, 0.999f, 1e-8f, nd ? 0.1f : 0.f, nd);
       opt.set_no_decay_norm_bias(nd);
+      float clip = 0.f;
+      for (int i = 1; i + 1 < argc; ++i)
+        if (std::string(argv[i]) == "--clip-ema") clip = (float)std::atof(argv[i + 1]);
+      if (clip > 0.f) {
+        opt.set_max_grad_norm(clip);
+        opt.set_ema_decay(0.9f);
+      }
       // --mix: every batch through a BatchMixer (Mixup 0.8 / CutMix 1.0, seed 7), trained against its
       // dense target with soft_crossentropy (label smoothing 0.1); --switch-to-labels: the last step
       // is fed the integer labels instead (a captured step must refuse them)
@@ -367,17 +380,27 @@ int main(int argc, char** argv) {
       bool graph = false;  // --graph: the GPU step captured once (TrainGraph) and replayed
       for (int i = 1; i < argc; ++i) graph = graph || std::string(argv[i]) == "--graph";
       TrainGraph tg(m, opt, loss);
+      if (clip > 0.f) m.save_to_file(std::string(argv[5]) + ".init");
       std::printf("losses");
       for (int i = 0; i < steps && data.next(batch, x, y); ++i) {
+        if (clip > 0.f) {
+          const std::string pre = std::string(argv[5]) + ".";
+          std::ofstream fx(pre + "x" + std::to_string(i) + ".bin", std::ios::binary);
+          x.to(Device::cpu()).save(fx);
+          std::vector<float> yl;
+          for (int64_t v : y.to(Device::cpu()).to_host_i64()) yl.push_back((float)v);
+          std::ofstream fy(pre + "y" + std::to_string(i) + ".bin", std::ios::binary);
+          Tensor::from_host(yl, {(int64_t)yl.size(), 1, 1, 1}, Device::cpu()).save(fy);
+        }
         if (mix && !(sw && i == steps - 1)) {
           Tensor xd = x.to(dev).clone(), t;
           mixer.mix(xd, y, t);
           x = xd;
           y = t;
         }
-        if (graph && dev.is_gpu()) {
-          tg.step(x, y);
-          std::printf(" %.6g", tg.last_loss());
+        if (graph && (dev.is_gpu() || clip > 0.f)) {
+          const double l = tg.step(x, y);
+          std::printf(" %.6g", dev.is_gpu() ? tg.last_loss() : l);
           continue;
         }
         m.zero_grad();
@@ -388,6 +411,12 @@ int main(int argc, char** argv) {
       }
       std::printf("\n");
       m.save_to_file(argv[5]);
+      if (clip > 0.f) {
+        std::printf("grad_norm %.9g\n", (double)opt.last_grad_norm());
+        opt.swap_ema(m.parameters());
+        m.save_to_file(std::string(argv[5]) + ".ema");
+        opt.swap_ema(m.parameters());
+      }
       return 0;
     }
   } catch (const std::exception& e) {
