@@ -10,8 +10,10 @@
 // same way (per-shape calls against a loop reference).
 #include <cstring>
 #include <exception>
+#include <stdexcept>
 #include <string>
 
+#include "../kernels/optim_segments.h"
 #include "dcnn/ops.hpp"
 #include "dcnn/tensor.hpp"
 
@@ -336,6 +338,90 @@ int dcnn_c_sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, 
 
 int dcnn_c_ema_swap(float* a, float* b, void* shadow, long n) {
   return guarded([&] { gpu_ops::ema_swap(a, b, shadow, n); });
+}
+
+// Layer-wise optimizers (LAMB, LARS) over flat fp32 buffers. dcnn_c_optim_segments builds the
+// segment / chunk tables from the slices (offsets / counts in elements, no_decay may be null, exclude:
+// flagged slices neither adapt nor decay) as flat int32 rows: chunks [*nchunks][3] = {first 64-element
+// block, blocks, segment}, segs [params][4] = {first chunk, chunks, adapt, decay}; *cover = the
+// element the chunks reach. With chunks == null only *nchunks and *cover are written (size query);
+// chunk_cap < *nchunks is an error. The device steps take the rows in device memory, part
+// [2 nchunks] and out [3 nsegs] device floats (out: trust, then {sum p^2, sum u^2}); hyper / coef /
+// ema optional. hp (doubles) = {lr, b1, b2, eps, bc1, bc2, wd} for LAMB, {lr, momentum, wd, tc, eps}
+// for LARS. The _host steps take host rows and out [3 nsegs] doubles.
+int dcnn_c_optim_segments(const long* offsets, const long* counts, const unsigned char* no_decay, int params,
+                          int exclude, long n, int* chunks, int chunk_cap, int* segs, int* nchunks, long* cover) {
+  try {
+    const OptimSegments t = build_optim_segments(offsets, counts, no_decay, params, exclude != 0, n);
+    *nchunks = (int)t.chunks.size();
+    *cover = t.cover;
+    if (!chunks) return 0;
+    if (chunk_cap < *nchunks || !segs)
+      throw std::invalid_argument("optim_segments: room for " + std::to_string(chunk_cap) + " chunk rows, " +
+                                  std::to_string(*nchunks) + " needed (and segs is required)");
+    for (size_t c = 0; c < t.chunks.size(); ++c) {
+      chunks[3 * c] = t.chunks[c].first_block;
+      chunks[3 * c + 1] = t.chunks[c].blocks;
+      chunks[3 * c + 2] = t.chunks[c].segment;
+    }
+    for (size_t k = 0; k < t.segs.size(); ++k) {
+      segs[4 * k] = t.segs[k].first_chunk;
+      segs[4 * k + 1] = t.segs[k].chunks;
+      segs[4 * k + 2] = t.segs[k].adapt;
+      segs[4 * k + 3] = t.segs[k].decay;
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+int dcnn_c_lamb_step(float* p, const float* g, float* m, float* v, void* shadow, long n, const double* hp,
+                     const float* hyper, const float* coef, float* ema, float decay, const void* chunks, int nchunks,
+                     const void* segs, int nsegs, long cover, float* part, float* out) {
+  return guarded([&] {
+    gpu_ops::lamb(p, g, m, v, shadow, n, (float)hp[0], hp[1], hp[2], (float)hp[3], (float)hp[4], (float)hp[5],
+                  (float)hp[6], hyper, coef, ema, decay, chunks, nchunks, segs, nsegs, cover, part, out);
+  });
+}
+
+int dcnn_c_lars_step(float* p, const float* g, float* vel, void* shadow, long n, const double* hp, const float* hyper,
+                     const float* coef, float* ema, float decay, const void* chunks, int nchunks, const void* segs,
+                     int nsegs, long cover, float* part, float* out) {
+  return guarded([&] {
+    gpu_ops::lars(p, g, vel, shadow, n, (float)hp[0], (float)hp[1], (float)hp[2], (float)hp[3], (float)hp[4], hyper,
+                  coef, ema, decay, chunks, nchunks, segs, nsegs, cover, part, out);
+  });
+}
+
+int dcnn_c_lamb_step_host(float* p, const float* g, float* m, float* v, long n, const double* hp, const double* coef,
+                          float* ema, float decay, const int* chunks, int nchunks, const int* segs, int nsegs,
+                          double* out) {
+  try {
+    check_optim_segments(reinterpret_cast<const SegChunk*>(chunks), nchunks, reinterpret_cast<const SegInfo*>(segs),
+                         nsegs, (n + kSegBlock - 1) / kSegBlock * kSegBlock);
+    cpu_ops::lamb(p, g, m, v, n, (float)hp[0], hp[1], hp[2], (float)hp[3], hp[4], hp[5], (float)hp[6], coef, ema, decay,
+                  chunks, nchunks, segs, nsegs, out);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
+}
+
+int dcnn_c_lars_step_host(float* p, const float* g, float* vel, long n, const double* hp, const double* coef, float* ema,
+                          float decay, const int* chunks, int nchunks, const int* segs, int nsegs, double* out) {
+  try {
+    check_optim_segments(reinterpret_cast<const SegChunk*>(chunks), nchunks, reinterpret_cast<const SegInfo*>(segs),
+                         nsegs, (n + kSegBlock - 1) / kSegBlock * kSegBlock);
+    cpu_ops::lars(p, g, vel, n, (float)hp[0], (float)hp[1], (float)hp[2], (float)hp[3], (float)hp[4], coef, ema, decay,
+                  chunks, nchunks, segs, nsegs, out);
+    return 0;
+  } catch (const std::exception& e) {
+    t_err = e.what();
+  }
+  return -1;
 }
 
 // the same on the CPU backend, host pointers: *sumsq the sum of g^2; coef null = no clipping

@@ -36,6 +36,7 @@ namespace dcnn {
 // weights: physical [Co][KH][KW][Ci] = NHWC of the logical (Co, Ci, KH, KW)); `shadow` is the bf16
 // GEMM operand copy on the GPU. `shape` is the logical 4-D shape of the .bin record.
 struct ParamArena;
+struct OptimSegments;  // csrc/kernels/optim_segments.h: the layer-wise optimizers' segment / chunk tables
 struct Param {
   std::string name;
   std::vector<int64_t> shape;
@@ -61,6 +62,12 @@ struct ParamArena {
   // weight EMA (an optimizer with set_ema_decay): a flat buffer of n floats, a copy of `value` when
   // it is created, updated inside the fused step; undefined while the EMA is off
   Tensor ema;
+  // layer-wise optimizers (LAMB, LARS): one segment per parameter, chunks of at most 4096 elements
+  // (built once by Sequential::pack_params with the kernel library's shared builder: static, so a
+  // captured step replays them as they are). segments[0]: every parameter adapts and decays;
+  // segments[1]: the Param::no_decay ones do neither. The chunk rows are the same for both.
+  std::shared_ptr<const OptimSegments> segments[2];
+  Tensor seg_chunks, seg_info[2];  // the device rows
   // every eligible conv's dgrad operand ([C][KH][KW][Co] bf16), regenerated from the shadows in
   // one batched launch after each fused optimizer step (rows: src, dst, Co, T, C)
   Tensor wt_table;
@@ -716,6 +723,15 @@ class Optimizer {
   void swap_ema(const std::vector<Param*>& params);
   // the gradient norm of the last step before clipping (synchronises the device); NaN with clipping off
   float last_grad_norm() const;
+  // What TrainGraph asks of an optimizer whose step it captures: the step reads its scalars (learning
+  // rate, step count) from device memory. step_count / set_step_count: the host mirror of the device
+  // counter; before_replay: a replay is about to run one step on the device (mirror it, upload a
+  // changed learning rate); upload_hyper: host state -> device scalars, outside a capture.
+  virtual bool capturable() const { return false; }
+  virtual long step_count() const { return 0; }
+  virtual void set_step_count(long t) { (void)t; }
+  virtual void before_replay() {}
+  virtual void upload_hyper() {}
 
  protected:
   bool tail() const { return max_norm_ > 0.f || ema_decay_ > 0.f; }
@@ -749,15 +765,16 @@ class Adam : public Optimizer {
   // the GPU arena path through the arena's block table and a second instance of the fused kernel
   void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
   bool no_decay_norm_bias() const { return no_decay_; }
-  long step_count() const { return t_; }
-  void set_step_count(long t) { t_ = t; }
+  bool capturable() const override { return true; }
+  long step_count() const override { return t_; }
+  void set_step_count(long t) override { t_ = t; }
   // a replayed graph ran one step on the device: mirror it on the host (t) and upload a changed
   // learning rate before the replay
-  void before_replay();
+  void before_replay() override;
   // host step state (lr, t) -> the device step scalars (outside a capture)
-  void upload_hyper();
+  void upload_hyper() override;
 
- private:
+ protected:
   float b1_, b2_, eps_, wd_;
   bool decoupled_;
   bool no_decay_ = false;
@@ -766,6 +783,64 @@ class Adam : public Optimizer {
   Tensor hyper_;
   float hyper_lr_ = -1.f;
   long hyper_t_ = -1;
+};
+
+// What LAMB and LARS share: a trust ratio per parameter from the L2 norms of its weights and of its
+// update, taken on the weights before the step. On a GPU arena the norms are one segmented fixed-order
+// reduction over the flat buffers (ParamArena::segments, csrc/kernels/layerwise.hip) and the trust
+// table stays on the device: two launches a step, no host read, capturable. With no_decay_norm_bias
+// a Param::no_decay parameter takes wd = 0 and trust 1. A zero norm gives trust 1; a non-finite
+// norm propagates into that parameter's step.
+class LayerwiseState {
+ public:
+  // the trust ratio of every parameter in the last step (synchronises the device): not for the hot path
+  std::vector<float> last_trust_ratios() const;
+
+ protected:
+  // GPU arena: the partials and the trust table for `a`'s tables (created outside a capture)
+  void workspace(ParamArena* a);
+  // per-parameter CPU path: parameter i as one segment of `n` elements
+  struct One {
+    std::vector<int> chunks, segs;
+  };
+  static One one_segment(long n, bool adapt);
+  Tensor part_, out_;           // GPU arena path
+  size_t nsegs_ = 0;
+  std::vector<double> trust_;   // per-parameter path
+};
+
+// LAMB (You et al. 2019): Adam's moments, r = (m / bc1) / (sqrt(v / bc2) + eps) + wd p, and
+// p -= lr trust r with trust = ||p|| / ||r|| per parameter. State and captured-step protocol as
+// Adam's (t, m, v). The betas are kept in double: the kernels take float(1 - beta).
+class LAMB : public Adam, public LayerwiseState {
+ public:
+  explicit LAMB(float lr = 1e-3f, double b1 = 0.9, double b2 = 0.999, float eps = 1e-6f, float wd = 0.01f)
+      : Adam(lr, (float)b1, (float)b2, eps, wd, false), b1d_(b1), b2d_(b2) {}
+  void step(const std::vector<Param*>& params) override;
+
+ private:
+  double b1d_, b2d_;
+};
+
+// LARS (You et al. 2017): trust = tc ||p|| / (||g|| + wd ||p|| + eps) per parameter,
+// v = mom v - lr trust (g + wd p), p += v (SGD's velocity convention and state; momentum 0: no velocity).
+class LARS : public SGD, public LayerwiseState {
+ public:
+  explicit LARS(float lr = 0.1f, float momentum = 0.9f, float wd = 5e-4f, float trust_coefficient = 1e-3f,
+                float eps = 1e-8f)
+      : SGD(lr, momentum), wd_(wd), tc_(trust_coefficient), eps_(eps) {}
+  void step(const std::vector<Param*>& params) override;
+  void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
+  bool no_decay_norm_bias() const { return no_decay_; }
+  bool capturable() const override { return true; }
+  void before_replay() override;
+  void upload_hyper() override;
+
+ private:
+  float wd_, tc_, eps_;
+  bool no_decay_ = false;
+  Tensor hyper_;  // GPU arena path: {lr} in device memory
+  float hyper_lr_ = -1.f;
 };
 
 

@@ -91,6 +91,16 @@ void adam_tail(float* p, const float* g, float* m, float* v, long n, float lr, f
 void sgd_tail(float* p, const float* g, float* vel, long n, float lr, float momentum, const double* coef, float* ema,
               float decay);
 void ema_swap(float* a, float* b, long n);
+// layer-wise optimizers over a buffer of n floats, driven by the flat int32 rows of the segment / chunk
+// tables (csrc/kernels/optim_segments.h: chunks [nchunks][3], segs [nsegs][4]); out [3 nsegs] doubles:
+// trust, then {sum p^2, sum u^2} per segment. A chunk is cut at n, so one unpadded parameter can be
+// stepped as a single segment. coef / ema: optional, null = off.
+void lamb(float* p, const float* g, float* m, float* v, long n, float lr, double b1, double b2, float eps, double bc1,
+          double bc2, float wd, const double* coef, float* ema, float decay, const int* chunks, int nchunks,
+          const int* segs, int nsegs, double* out);
+void lars(float* p, const float* g, float* vel, long n, float lr, float momentum, float wd, float tc, float eps,
+          const double* coef, float* ema, float decay, const int* chunks, int nchunks, const int* segs, int nsegs,
+          double* out);
 // stochastic depth: mask[n] = 0 or 1 / (1 - p) from (seed, draw), the one function of the kernel
 // library and the native backend; y[n][:] = mask[n] x[n][:] over samples of `row` elements
 void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw);
@@ -354,6 +364,19 @@ void adam_tail(float* p, const float* g, float* m, float* v, void* shadow, long 
 void sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum, const float* coef,
               float* ema, float decay);
 void ema_swap(float* a, float* b, void* shadow, long n);
+// layer-wise optimizers (layerwise.hip), two launches a step on the current flow. chunks / segs: the
+// device rows of the tables, cover: the element the chunks reach; part [2 nchunks] and out [3 nsegs]
+// device floats (out: trust, then {sum p^2, sum u^2} per segment). layerwise_workspace creates and zeroes
+// the self-resetting ticket word outside any capture. lamb_scalars: hyper = {lr, bc1, bc2, t}, t += 1
+// and the bias corrections in double; with hyper set, lamb / lars read lr (and bc1, bc2) from it.
+void layerwise_workspace();
+void lamb_scalars(float* hyper, double b1, double b2);
+void lamb(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, double b1, double b2,
+          float eps, float bc1, float bc2, float wd, const float* hyper, const float* coef, float* ema, float decay, const void* chunks, int nchunks,
+          const void* segs, int nsegs, long cover, float* part, float* out);
+void lars(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum, float wd, float tc,
+          float eps, const float* hyper, const float* coef, float* ema, float decay, const void* chunks, int nchunks,
+          const void* segs, int nsegs, long cover, float* part, float* out);
 // stochastic depth (droppath.hip, bf16 activations). drop_path_draw: *slot = ++*ctr on the device,
 // then the mask of (seed, *slot) into mask[N] (a captured step draws a new mask at every replay);
 // drop_path_mask: the mask of a given draw index. drop_path_scale: y[n] = mask[n] x[n] (+ residual)

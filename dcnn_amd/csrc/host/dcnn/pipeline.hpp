@@ -66,7 +66,7 @@ struct StageConfig {
 std::unique_ptr<dcnn_native::Communicator> make_tcp_communicator(const std::string& id, const std::string& host,
                                                                  int port, int* bound_port = nullptr);
 
-// {"type": "sgd" | "adam" | "adamw", "parameters": {...}} (the Python OptimizerConfig)
+// {"type": "sgd" | "adam" | "adamw" | "lamb" | "lars", "parameters": {...}} (the Python OptimizerConfig)
 std::unique_ptr<Optimizer> create_optimizer(const json::Value& cfg);
 
 // flat state of a run of layers: every parameter in checkpoint order, then every BatchNorm's

@@ -12,6 +12,7 @@
 #include <functional>
 #include <initializer_list>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -55,7 +56,12 @@ class Loss {
 // changed, so the first replay is the first update.
 class TrainGraph {
  public:
-  TrainGraph(Sequential& model, Adam& opt, const Loss& loss) : model_(model), opt_(opt), loss_(loss) {}
+  // opt: an optimizer whose step reads its scalars from device memory (Adam / AdamW, LAMB, LARS)
+  TrainGraph(Sequential& model, Optimizer& opt, const Loss& loss) : model_(model), opt_(opt), loss_(loss) {
+    if (!opt.capturable())
+      throw std::invalid_argument("TrainGraph: this optimizer's step cannot be captured (its step scalars are "
+                                  "kernel arguments, not device memory)");
+  }
   // eager on the first call: captures, then replays. y: int64 labels [N] or an fp32 target [N, C];
   // the static slot takes the first batch's dtype and shape, another one later throws
   double step(const Tensor& x, const Tensor& y);
@@ -67,7 +73,7 @@ class TrainGraph {
  private:
   void capture(const Tensor& x, const Tensor& labels);
   Sequential& model_;
-  Adam& opt_;
+  Optimizer& opt_;
   const Loss& loss_;
   gpu::Graph graph_;
   Tensor sx_, sy_;

@@ -2,6 +2,7 @@
 #include "dcnn/nn.hpp"
 
 #include "../kernels/fusion_plan.h"
+#include "../kernels/optim_segments.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1761,6 +1762,28 @@ void Sequential::pack_params() {
     A->nodecay = Tensor::empty({(int64_t)tab.size()}, DType::U8, dev_);
     gpu::copy(A->nodecay.data(), tab.data(), tab.size(), 0);
   }
+  // the layer-wise optimizers' segment / chunk tables (static): [1] excludes the no_decay parameters
+  {
+    std::vector<long> offs, counts;
+    std::vector<unsigned char> flags;
+    for (size_t k = 0; k < ps.size(); ++k) {
+      offs.push_back((long)off[k]);
+      counts.push_back((long)ps[k]->value.numel());
+      flags.push_back(ps[k]->no_decay ? 1 : 0);
+    }
+    for (int e = 0; e < 2; ++e) {
+      auto t = std::make_shared<OptimSegments>(
+          build_optim_segments(offs.data(), counts.data(), flags.data(), (int)ps.size(), e == 1, (long)A->n));
+      check_optim_segments(t->chunks.data(), (int)t->chunks.size(), t->segs.data(), (int)t->segs.size(), (long)A->n);
+      A->seg_info[e] = Tensor::empty({(int64_t)(t->segs.size() * sizeof(SegInfo))}, DType::U8, dev_);
+      gpu::copy(A->seg_info[e].data(), t->segs.data(), t->segs.size() * sizeof(SegInfo), 0);
+      if (e == 0 && !t->chunks.empty()) {
+        A->seg_chunks = Tensor::empty({(int64_t)(t->chunks.size() * sizeof(SegChunk))}, DType::U8, dev_);
+        gpu::copy(A->seg_chunks.data(), t->chunks.data(), t->chunks.size() * sizeof(SegChunk), 0);
+      }
+      A->segments[e] = t;
+    }
+  }
   // the convs' pre-transposed dgrad operands (from the arena shadows)
   std::vector<Layer*> all;
   for (auto& l : layers_) l->collect_layers(all);
@@ -2422,6 +2445,126 @@ void Adam::step(const std::vector<Param*>& params) {
     else
       cpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
                     p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
+  }
+}
+
+// ------------------------------------------------------------------ layer-wise optimizers
+void LayerwiseState::workspace(ParamArena* a) {
+  const OptimSegments& t = *a->segments[0];
+  if (part_.defined() && nsegs_ == t.segs.size()) return;
+  if (gpu::Graph::capturing()) throw std::runtime_error("layer-wise optimizer: workspace created inside a graph capture");
+  nsegs_ = t.segs.size();
+  part_ = Tensor::zeros({(int64_t)std::max<size_t>((size_t)kSegPartFloats * t.chunks.size(), 1)}, DType::F32, a->value.device());
+  out_ = Tensor::zeros({(int64_t)std::max<size_t>(3 * nsegs_, 1)}, DType::F32, a->value.device());
+  gpu_ops::layerwise_workspace();
+}
+
+LayerwiseState::One LayerwiseState::one_segment(long n, bool adapt) {
+  const long off = 0;
+  const OptimSegments t = build_optim_segments(&off, &n, nullptr, 1, false, (n + kSegBlock - 1) / kSegBlock * kSegBlock);
+  One o;
+  for (const SegChunk& c : t.chunks) o.chunks.insert(o.chunks.end(), {c.first_block, c.blocks, c.segment});
+  for (const SegInfo& g : t.segs) o.segs.insert(o.segs.end(), {g.first_chunk, g.chunks, adapt ? 1 : 0, adapt ? 1 : 0});
+  return o;
+}
+
+std::vector<float> LayerwiseState::last_trust_ratios() const {
+  if (!out_.defined()) return std::vector<float>(trust_.begin(), trust_.end());
+  gpu::flow_synchronize();
+  std::vector<float> h(nsegs_);
+  if (nsegs_) gpu::copy(h.data(), out_.data(), nsegs_ * sizeof(float), 1);
+  return h;
+}
+
+void LAMB::step(const std::vector<Param*>& params) {
+  if (tail()) prepare(params);
+  if (ParamArena* a = whole_arena(params)) {
+    workspace(a);
+    if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
+    if (hyper_lr_ != lr_ || hyper_t_ != t_) {
+      if (gpu::Graph::capturing()) throw std::runtime_error("LAMB: step scalars changed inside a graph capture");
+      upload_hyper();
+    }
+    ++t_;
+    ++hyper_t_;
+    gpu_ops::lamb_scalars(hyper_.ptr<float>(), b1d_, b2d_);
+    const OptimSegments& t = *a->segments[no_decay_ ? 1 : 0];
+    gpu_ops::lamb(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(), a->shadow.data(),
+                  (long)a->n, lr_, b1d_, b2d_, eps_, 1.f, 1.f, wd_, hyper_.ptr<float>(), launch_norm(a),
+                  ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_, a->seg_chunks.data(),
+                  (int)t.chunks.size(), a->seg_info[no_decay_ ? 1 : 0].data(), (int)t.segs.size(), t.cover,
+                  part_.ptr<float>(), out_.ptr<float>());
+    a->refresh_transposes();
+    return;
+  }
+  ++t_;
+  const double bc1 = 1.0 - std::pow(b1d_, (double)t_), bc2 = 1.0 - std::pow(b2d_, (double)t_);
+  double coef = 1.0;
+  const bool clip = host_coef(params, &coef);
+  trust_.assign(params.size(), 1.0);
+  for (size_t i = 0; i < params.size(); ++i) {
+    Param* p = params[i];
+    if (p->value.device().is_gpu()) throw std::runtime_error("LAMB on the GPU needs all parameters of one arena");
+    if (!p->m.defined()) {
+      p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
+      p->v = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
+    }
+    if (ema_decay_ > 0.f && !p->ema.defined()) p->ema = p->value.clone();
+    const One o = one_segment((long)p->value.numel(), !(no_decay_ && p->no_decay));
+    double out[3] = {1.0, 0.0, 0.0};
+    cpu_ops::lamb(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
+                  (long)p->value.numel(), lr_, b1d_, b2d_, eps_, bc1, bc2, wd_, clip ? &coef : nullptr,
+                  ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_, o.chunks.data(),
+                  (int)o.chunks.size() / 3, o.segs.data(), 1, out);
+    trust_[i] = out[0];
+  }
+}
+
+void LARS::upload_hyper() {
+  if (!hyper_.defined()) return;
+  const float h[4] = {lr_, 0.f, 0.f, 0.f};
+  gpu::copy(hyper_.data(), h, sizeof h, 0);
+  hyper_lr_ = lr_;
+}
+
+void LARS::before_replay() {
+  if (hyper_.defined() && hyper_lr_ != lr_) upload_hyper();
+}
+
+void LARS::step(const std::vector<Param*>& params) {
+  if (tail()) prepare(params);
+  const float mom = momentum();
+  if (ParamArena* a = whole_arena(params)) {
+    workspace(a);
+    if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
+    if (hyper_lr_ != lr_) {
+      if (gpu::Graph::capturing()) throw std::runtime_error("LARS: the learning rate changed inside a graph capture");
+      upload_hyper();
+    }
+    const OptimSegments& t = *a->segments[no_decay_ ? 1 : 0];
+    gpu_ops::lars(a->value.ptr<float>(), a->grad.ptr<float>(), mom != 0.f ? a->m.ptr<float>() : nullptr,
+                  a->shadow.data(), (long)a->n, lr_, mom, wd_, tc_, eps_, hyper_.ptr<float>(), launch_norm(a),
+                  ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_, a->seg_chunks.data(),
+                  (int)t.chunks.size(), a->seg_info[no_decay_ ? 1 : 0].data(), (int)t.segs.size(), t.cover,
+                  part_.ptr<float>(), out_.ptr<float>());
+    a->refresh_transposes();
+    return;
+  }
+  double coef = 1.0;
+  const bool clip = host_coef(params, &coef);
+  trust_.assign(params.size(), 1.0);
+  for (size_t i = 0; i < params.size(); ++i) {
+    Param* p = params[i];
+    if (p->value.device().is_gpu()) throw std::runtime_error("LARS on the GPU needs all parameters of one arena");
+    if (mom != 0.f && !p->m.defined()) p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
+    if (ema_decay_ > 0.f && !p->ema.defined()) p->ema = p->value.clone();
+    const One o = one_segment((long)p->value.numel(), !(no_decay_ && p->no_decay));
+    double out[3] = {1.0, 0.0, 0.0};
+    cpu_ops::lars(p->value.ptr<float>(), p->grad.ptr<float>(), mom != 0.f ? p->m.ptr<float>() : nullptr,
+                  (long)p->value.numel(), lr_, mom, wd_, tc_, eps_, clip ? &coef : nullptr,
+                  ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_, o.chunks.data(),
+                  (int)o.chunks.size() / 3, o.segs.data(), 1, out);
+    trust_[i] = out[0];
   }
 }
 

@@ -199,6 +199,16 @@ void sgd_tail(float* p, const float* g, float* vel, long n, float lr, float mome
 }
 
 void ema_swap(float* a, float* b, long n) { C::ema_swap<float>(a, b, n); }
+void lamb(float* p, const float* g, float* m, float* v, long n, float lr, double b1, double b2, float eps, double bc1,
+          double bc2, float wd, const double* coef, float* ema, float decay, const int* chunks, int nchunks,
+          const int* segs, int nsegs, double* out) {
+  C::lamb_step<float>(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, coef, ema, decay, chunks, nchunks, segs, nsegs, out);
+}
+void lars(float* p, const float* g, float* vel, long n, float lr, float momentum, float wd, float tc, float eps,
+          const double* coef, float* ema, float decay, const int* chunks, int nchunks, const int* segs, int nsegs,
+          double* out) {
+  C::lars_step<float>(p, g, vel, n, lr, momentum, wd, tc, eps, coef, ema, decay, chunks, nchunks, segs, nsegs, out);
+}
 
 }  // namespace cpu_ops
 }  // namespace dcnn

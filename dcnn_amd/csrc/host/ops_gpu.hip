@@ -344,7 +344,8 @@ inline hipStream_t cur() { return static_cast<hipStream_t>(gpu::flow()); }
 
 // grow-only workspace per purpose
 enum Slot { W_T = 0, SLAB, BSLAB, STAT_SLAB, STAT_SUMS, STAT_PART, LOSS_WS, LOSS_OUT, TICKETS, HPART, HTICKETS, GN_AFF,
-            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, LN_WS, GNORM_PART, GNORM_TICKET, NSLOTS };
+            FWD_STATS, BWD_STATS, FWD_STATS2, STAT_SLAB2, STAT_SUMS2, STAT_PART2, LN_WS, GNORM_PART, GNORM_TICKET, LW_TICKET,
+            NSLOTS };
 void* scratch(Slot s, size_t bytes) {
   static void* p[NSLOTS] = {};
   static size_t n[NSLOTS] = {};
@@ -1279,6 +1280,40 @@ void sgd_tail(float* p, const float* g, float* vel, void* shadow, long n, float 
 
 void ema_swap(float* a, float* b, void* shadow, long n) {
   dcnn::ema_swap(a, b, static_cast<bf16*>(shadow), n, cur());
+}
+
+void layerwise_workspace() {
+  static bool zeroed = false;  // zeroed once; every launch leaves the ticket zeroed
+  void* t = scratch(LW_TICKET, 64 * 4);
+  if (!zeroed) {
+    HOST_HIP_CHECK(hipMemsetAsync(t, 0, 64 * 4, cur()));
+    zeroed = true;
+  }
+}
+
+void lamb_scalars(float* hyper, double b1, double b2) { dcnn::lamb_scalars(hyper, b1, b2, cur()); }
+
+namespace {
+LayerwiseTables lw_tables(const void* chunks, int nchunks, const void* segs, int nsegs, long cover, float* part,
+                          float* out) {
+  if (!gpu::Graph::capturing()) layerwise_workspace();  // (a capture finds what the warm-up steps created)
+  return LayerwiseTables{static_cast<const SegChunk*>(chunks), nchunks, static_cast<const SegInfo*>(segs), nsegs, cover,
+                         part, static_cast<unsigned*>(scratch(LW_TICKET, 0)), out};
+}
+}  // namespace
+
+void lamb(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, double b1, double b2,
+          float eps, float bc1, float bc2, float wd, const float* hyper, const float* coef, float* ema, float decay, const void* chunks, int nchunks,
+          const void* segs, int nsegs, long cover, float* part, float* out) {
+  lamb_step(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, hyper, coef, ema, decay,
+            lw_tables(chunks, nchunks, segs, nsegs, cover, part, out), cur());
+}
+
+void lars(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum, float wd, float tc,
+          float eps, const float* hyper, const float* coef, float* ema, float decay, const void* chunks, int nchunks,
+          const void* segs, int nsegs, long cover, float* part, float* out) {
+  lars_step(p, g, vel, static_cast<bf16*>(shadow), n, lr, momentum, wd, tc, eps, hyper, coef, ema, decay,
+            lw_tables(chunks, nchunks, segs, nsegs, cover, part, out), cur());
 }
 
 }  // namespace gpu_ops

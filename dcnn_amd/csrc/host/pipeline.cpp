@@ -184,6 +184,22 @@ std::unique_ptr<Optimizer> create_optimizer(const json::Value& cfg) {
     return std::make_unique<Adam>(lr, (float)p.get_number("beta1", 0.9), (float)p.get_number("beta2", 0.999),
                                   (float)p.get_number("epsilon", 1e-8), (float)p.get_number("weight_decay", 0.0), dec);
   }
+  // (a trust ratio is local to a parameter, so a stage's LAMB / LARS step is the model's step)
+  if (type == "lamb") {
+    auto o = std::make_unique<LAMB>((float)p.get_number("learning_rate", 1e-3), p.get_number("beta1", 0.9),
+                                    p.get_number("beta2", 0.999), (float)p.get_number("epsilon", 1e-6),
+                                    (float)p.get_number("weight_decay", 0.01));
+    o->set_no_decay_norm_bias(p.get_bool("no_decay_norm_bias", false));
+    return o;
+  }
+  if (type == "lars") {
+    auto o = std::make_unique<LARS>((float)p.get_number("learning_rate", 0.1), (float)p.get_number("momentum", 0.9),
+                                    (float)p.get_number("weight_decay", 5e-4),
+                                    (float)p.get_number("trust_coefficient", 1e-3),
+                                    (float)p.get_number("epsilon", 1e-8));
+    o->set_no_decay_norm_bias(p.get_bool("no_decay_norm_bias", false));
+    return o;
+  }
   throw std::runtime_error("unknown optimizer type '" + type + "'");
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "fusion_plan.h"  // the shared fusion planner (both front ends)
+#include "optim_segments.h"  // segment / chunk tables of the layer-wise optimizers (both front ends)
 typedef __bf16 bf16;
 
 namespace dcnn {
@@ -406,6 +407,37 @@ void sgd_step_tail(float* p, const float* g, float* vel, bf16* shadow, long n, f
                    const float* coef, float* ema, float decay, hipStream_t s);
 // exchange the flat fp32 buffers a and b, shadow (optional) = bf16 of the new a; twice restores every bit
 void ema_swap(float* a, float* b, bf16* shadow, long n, hipStream_t s);
+// Layer-wise optimizers (layerwise.hip): LAMB and LARS over the flat arena, two launches a step. The
+// chunk and segment tables (optim_segments.h) are static device memory; cover is the element the
+// chunks reach (the buffers hold at least that many, checked with the numbers in the message); part
+// [2 x nchunks] (kSegPartFloats a chunk) holds the per-chunk partial pairs, ticket is a self-resetting word per stream, out
+// [3 x nsegs] receives trust [nsegs] and then the pairs {sum p^2, sum u^2} (u: LAMB's update r, LARS's
+// gradient). hyper / coef / ema are optional (null = off) as in the tail kernels: hyper = {lr, bc1,
+// bc2} for LAMB, {lr} for LARS. A segment that does not adapt, or whose weight or update norm is
+// zero, has trust 1; a non-finite norm propagates. fp32, buffers 16-byte aligned.
+struct LayerwiseTables {
+  const SegChunk* chunks;
+  int nchunks;
+  const SegInfo* segs;
+  int nsegs;
+  long cover;
+  float* part;
+  unsigned* ticket;
+  float* out;
+};
+// r = (m / bc1) / (sqrt(v / bc2) + eps) + wd_i p, p -= lr trust_i r with trust_i = ||p_i|| / ||r_i||
+// (the betas in double: the kernel takes float(1 - beta), not 1 - float(beta))
+void lamb_step(float* p, const float* g, float* m, float* v, bf16* shadow, long n, float lr, double b1, double b2,
+               float eps, float bc1, float bc2, float wd, const float* hyper, const float* coef, float* ema,
+               float decay, const LayerwiseTables& t, hipStream_t s);
+// hyper = {lr, bc1, bc2, t} on the device: t += 1, bc = 1 - beta^t computed in double (adam_scalars'
+// role for LAMB; captured ahead of lamb_step, so a replay needs no host upload)
+void lamb_scalars(float* hyper, double b1, double b2, hipStream_t s);
+// trust_i = tc ||p_i|| / (coef ||g_i|| + wd_i ||p_i|| + eps); v = mom v - lr trust_i (g + wd_i p), p += v
+// (vel null: p -= lr trust_i (g + wd_i p))
+void lars_step(float* p, const float* g, float* vel, bf16* shadow, long n, float lr, float mom, float wd, float tc,
+               float eps, const float* hyper, const float* coef, float* ema, float decay, const LayerwiseTables& t,
+               hipStream_t s);
 // data-parallel bf16 gradient wire format (comm.hip)
 void grad_pack_bf16(const float* g, bf16* out, long n, float scale, hipStream_t s);
 void grad_sum_chunks_bf16(const bf16* src, int w, long ld, long n, bf16* dst, hipStream_t s);

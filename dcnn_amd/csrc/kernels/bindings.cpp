@@ -691,6 +691,49 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("ema_swap", [](uintptr_t a, uintptr_t b, uintptr_t shadow, long n, uintptr_t st) {
     ema_swap(P<float*>(a), P<float*>(b), P<bf16*>(shadow), n, S(st));
   });
+  // layer-wise optimizers: the shared table builder (optim_segments.cpp; rows flattened to int32:
+  // chunks [n][3] = {first block, blocks, segment}, segs [n][4] = {first chunk, chunks, adapt, decay})
+  // and the two-launch steps (layerwise.hip)
+  m.def("optim_segments", [](const std::vector<long>& offsets, const std::vector<long>& counts,
+                             const std::vector<int>& no_decay, bool exclude, long n) {
+    if (offsets.size() != counts.size() || (!no_decay.empty() && no_decay.size() != counts.size()))
+      throw std::invalid_argument("optim_segments: offsets, counts and no_decay have one entry per parameter");
+    std::vector<unsigned char> nd(no_decay.begin(), no_decay.end());
+    const OptimSegments t = build_optim_segments(offsets.data(), counts.data(), nd.empty() ? nullptr : nd.data(),
+                                                 (int)counts.size(), exclude, n);
+    std::vector<int> c, s;
+    for (const SegChunk& k : t.chunks) c.insert(c.end(), {k.first_block, k.blocks, k.segment});
+    for (const SegInfo& g : t.segs) s.insert(s.end(), {g.first_chunk, g.chunks, g.adapt, g.decay});
+    return py::make_tuple(c, s, t.cover);
+  });
+  m.def("optim_segments_check", [](const std::vector<int>& chunks, const std::vector<int>& segs, long n) {
+    static_assert(sizeof(SegChunk) == 3 * sizeof(int) && sizeof(SegInfo) == 4 * sizeof(int), "flat int32 rows");
+    if (chunks.size() % 3 || segs.size() % 4)
+      throw std::invalid_argument("optim_segments_check: chunk rows have 3 and segment rows 4 entries");
+    check_optim_segments(reinterpret_cast<const SegChunk*>(chunks.data()), (int)(chunks.size() / 3),
+                         reinterpret_cast<const SegInfo*>(segs.data()), (int)(segs.size() / 4), n);
+  });
+  m.def("lamb_scalars", [](uintptr_t hyper, double b1, double b2, uintptr_t st) {
+    lamb_scalars(P<float*>(hyper), b1, b2, S(st));
+  });
+  m.def("lamb_step", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t shadow, long n, float lr,
+                        double b1, double b2, float eps, float bc1, float bc2, float wd, uintptr_t hyper, uintptr_t coef,
+                        uintptr_t ema, float decay, uintptr_t chunks, int nchunks, uintptr_t segs, int nsegs,
+                        long cover, uintptr_t part, uintptr_t ticket, uintptr_t out, uintptr_t st) {
+    const LayerwiseTables t{P<const SegChunk*>(chunks), nchunks, P<const SegInfo*>(segs), nsegs, cover,
+                            P<float*>(part), P<unsigned*>(ticket), P<float*>(out)};
+    lamb_step(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(shadow), n, lr, b1, b2, eps, bc1,
+              bc2, wd, P<const float*>(hyper), P<const float*>(coef), P<float*>(ema), decay, t, S(st));
+  });
+  m.def("lars_step", [](uintptr_t p, uintptr_t g, uintptr_t vel, uintptr_t shadow, long n, float lr, float mom, float wd,
+                        float tc, float eps, uintptr_t hyper, uintptr_t coef, uintptr_t ema, float decay,
+                        uintptr_t chunks, int nchunks, uintptr_t segs, int nsegs, long cover, uintptr_t part,
+                        uintptr_t ticket, uintptr_t out, uintptr_t st) {
+    const LayerwiseTables t{P<const SegChunk*>(chunks), nchunks, P<const SegInfo*>(segs), nsegs, cover,
+                            P<float*>(part), P<unsigned*>(ticket), P<float*>(out)};
+    lars_step(P<float*>(p), P<const float*>(g), P<float*>(vel), P<bf16*>(shadow), n, lr, mom, wd, tc, eps,
+              P<const float*>(hyper), P<const float*>(coef), P<float*>(ema), decay, t, S(st));
+  });
   m.def("zero_bytes", [](uintptr_t p, long nbytes, uintptr_t st) { zero_bytes(P<void*>(p), nbytes, S(st)); });
   m.def("grad_pack_bf16", [](uintptr_t g, uintptr_t out, long n, float scale, uintptr_t st) {
     grad_pack_bf16(P<const float*>(g), P<bf16*>(out), n, scale, S(st));

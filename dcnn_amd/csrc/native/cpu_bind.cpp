@@ -231,6 +231,21 @@ void bind_cpu(py::module_& parent) {
   m.def("ema_swap", [](int dt, uintptr_t a, uintptr_t b, long n) {
     DT_DISPATCH(dt, ema_swap<T>(P<T>(a), P<T>(b), n));
   }, Rel());
+  // layer-wise optimizers: chunks / segs are int32 host tables (rows of 3 / 4), out 3 * nsegs doubles
+  m.def("lamb_step", [](int dt, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, long n, double lr, double b1,
+                        double b2, double eps, double bc1, double bc2, double wd, bool clip, double coef, uintptr_t ema,
+                        double decay, uintptr_t chunks, int nchunks, uintptr_t segs, int nsegs, uintptr_t out) {
+    DT_DISPATCH(dt, lamb_step<T>(P<T>(p), P<const T>(g), P<T>(mm), P<T>(v), n, lr, b1, b2, eps, bc1, bc2, wd,
+                                 clip ? &coef : nullptr, P<T>(ema), decay, P<const int>(chunks), nchunks,
+                                 P<const int>(segs), nsegs, P<double>(out)));
+  }, Rel());
+  m.def("lars_step", [](int dt, uintptr_t p, uintptr_t g, uintptr_t vel, long n, double lr, double mom, double wd,
+                        double tc, double eps, bool clip, double coef, uintptr_t ema, double decay, uintptr_t chunks,
+                        int nchunks, uintptr_t segs, int nsegs, uintptr_t out) {
+    DT_DISPATCH(dt, lars_step<T>(P<T>(p), P<const T>(g), P<T>(vel), n, lr, mom, wd, tc, eps, clip ? &coef : nullptr,
+                                 P<T>(ema), decay, P<const int>(chunks), nchunks, P<const int>(segs), nsegs,
+                                 P<double>(out)));
+  }, Rel());
   // the N mask values of stochastic depth for (seed, draw), as a list
   m.def("drop_path_mask", [](uint64_t seed, uint64_t draw, long N, double p) {
     if (N < 1) throw std::invalid_argument("drop_path_mask: N < 1");

@@ -112,6 +112,22 @@ template <typename T>
 void sgd_step_tail(T* p, const T* g, T* vel, long n, double lr, double momentum, const double* coef, T* ema,
                    double decay);
 template <typename T> void ema_swap(T* a, T* b, long n);
+// Layer-wise optimizers over the flat buffer, driven by the GPU's segment / chunk tables
+// (csrc/kernels/optim_segments.h) as flat int32 rows: chunks [nchunks][3] = {first 64-element block,
+// blocks, segment}, segs [nsegs][4] = {first chunk, chunks, adapt, decay}. Norms are double partials per
+// chunk in element order, added per segment in chunk order. out [3 nsegs]: trust, then {sum p^2, sum
+// u^2} per segment. LAMB: r = (m / bc1) / (sqrt(v / bc2) + eps) + wd_i p, p -= lr trust_i r, trust_i =
+// ||p_i|| / ||r_i||. LARS: trust_i = tc ||p_i|| / (coef ||g_i|| + wd_i ||p_i|| + eps), v = mom v - lr
+// trust_i (g + wd_i p), p += v. trust_i = 1 where the segment does not adapt or a norm is zero; a
+// non-finite norm propagates. coef / ema as in the tail steps.
+template <typename T>
+void lamb_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+               double bc2, double wd, const double* coef, T* ema, double decay, const int* chunks, int nchunks,
+               const int* segs, int nsegs, double* out);
+template <typename T>
+void lars_step(T* p, const T* g, T* vel, long n, double lr, double momentum, double wd, double tc, double eps,
+               const double* coef, T* ema, double decay, const int* chunks, int nchunks, const int* segs, int nsegs,
+               double* out);
 // stochastic depth: mask[n] = 0 or 1 / (1 - p), the GPU's mask (csrc/kernels/droppath.hip) bit for
 // bit; y[n][:] = mask[n] x[n][:] over samples of `row` contiguous elements
 void drop_path_mask(float* mask, long N, double p, uint64_t seed, uint64_t draw);

@@ -1567,6 +1567,107 @@ void ema_swap(T* a, T* b, long n) {
   });
 }
 
+// ------------------------------------------------------------------ layer-wise optimizers (LAMB, LARS)
+// The GPU's tables (csrc/kernels/optim_segments.h) as flat int32 rows: chunks [nchunks][3] = {first
+// 64-element block, blocks, segment}, segs [nsegs][4] = {first chunk, chunks, adapt, decay}. A chunk's
+// sums are double partials over its elements in order, a segment's sum its chunks' partials in chunk
+// order. out [3 nsegs] doubles: trust, then the pairs {sum p^2, sum u^2}. A chunk is cut at the
+// buffer's n elements, so a lone unpadded parameter can be stepped as one segment.
+static inline double lamb_r(double p, double m, double v, double bc1, double bc2, double eps, double wd) {
+  return (m / bc1) / (std::sqrt(v / bc2) + eps) + wd * p;
+}
+
+template <typename F>
+static void segment_trust(const int* segs, int nsegs, const std::vector<double>& part, double* out, F&& trust_of) {
+  for (int s = 0; s < nsegs; ++s) {
+    const int* g = segs + 4 * (long)s;
+    double a = 0.0, b = 0.0;
+    for (int k = 0; k < g[1]; ++k) {
+      a += part[2 * ((long)g[0] + k)];
+      b += part[2 * ((long)g[0] + k) + 1];
+    }
+    out[s] = g[2] ? trust_of(a, b, g[3]) : 1.0;
+    out[nsegs + 2 * (long)s] = a;
+    out[nsegs + 2 * (long)s + 1] = b;
+  }
+}
+
+template <typename T>
+void lamb_step(T* p, const T* g, T* m, T* v, long n, double lr, double b1, double b2, double eps, double bc1,
+               double bc2, double wd, const double* coef, T* ema, double decay, const int* chunks, int nchunks,
+               const int* segs, int nsegs, double* out) {
+  const double c = coef ? *coef : 1.0;
+  std::vector<double> part(2 * (size_t)(nchunks > 0 ? nchunks : 0), 0.0);
+  ThreadPool::instance().run(nchunks, [&](long k) {
+    const int* ch = chunks + 3 * k;
+    const double w = segs[4 * (long)ch[2] + 3] ? wd : 0.0;
+    const long lo = (long)ch[0] * 64, hi = std::min(lo + (long)ch[1] * 64, n);
+    double a = 0.0, b = 0.0;
+    for (long i = lo; i < hi; ++i) {
+      const double gi = coef ? g[i] * c : (double)g[i];
+      m[i] = (T)(b1 * m[i] + (1.0 - b1) * gi);
+      v[i] = (T)(b2 * v[i] + (1.0 - b2) * gi * gi);
+      const double pi = p[i], r = lamb_r(pi, m[i], v[i], bc1, bc2, eps, w);
+      a += pi * pi;
+      b += r * r;
+    }
+    part[2 * k] = a;
+    part[2 * k + 1] = b;
+  });
+  segment_trust(segs, nsegs, part, out, [](double sp, double sr, int) {
+    const double pn = std::sqrt(sp), rn = std::sqrt(sr);
+    return (pn == 0.0 || rn == 0.0) ? 1.0 : pn / rn;
+  });
+  ThreadPool::instance().run(nchunks, [&](long k) {
+    const int* ch = chunks + 3 * k;
+    const double w = segs[4 * (long)ch[2] + 3] ? wd : 0.0, s = lr * out[ch[2]];
+    const long lo = (long)ch[0] * 64, hi = std::min(lo + (long)ch[1] * 64, n);
+    for (long i = lo; i < hi; ++i) {
+      p[i] -= (T)(s * lamb_r(p[i], m[i], v[i], bc1, bc2, eps, w));
+      if (ema) ema[i] = (T)(decay * ema[i] + (1.0 - decay) * p[i]);
+    }
+  });
+}
+
+template <typename T>
+void lars_step(T* p, const T* g, T* vel, long n, double lr, double momentum, double wd, double tc, double eps,
+               const double* coef, T* ema, double decay, const int* chunks, int nchunks, const int* segs, int nsegs,
+               double* out) {
+  const double c = coef ? *coef : 1.0;
+  std::vector<double> part(2 * (size_t)(nchunks > 0 ? nchunks : 0), 0.0);
+  ThreadPool::instance().run(nchunks, [&](long k) {
+    const int* ch = chunks + 3 * k;
+    const long lo = (long)ch[0] * 64, hi = std::min(lo + (long)ch[1] * 64, n);
+    double a = 0.0, b = 0.0;
+    for (long i = lo; i < hi; ++i) {
+      const double pi = p[i], gi = g[i];
+      a += pi * pi;
+      b += gi * gi;
+    }
+    part[2 * k] = a;
+    part[2 * k + 1] = b;
+  });
+  segment_trust(segs, nsegs, part, out, [&](double sp, double sg, int dec) {
+    const double pn = std::sqrt(sp), gn = c * std::sqrt(sg);
+    return (pn == 0.0 || gn == 0.0) ? 1.0 : tc * pn / (gn + (dec ? wd : 0.0) * pn + eps);
+  });
+  ThreadPool::instance().run(nchunks, [&](long k) {
+    const int* ch = chunks + 3 * k;
+    const double w = segs[4 * (long)ch[2] + 3] ? wd : 0.0, s = lr * out[ch[2]];
+    const long lo = (long)ch[0] * 64, hi = std::min(lo + (long)ch[1] * 64, n);
+    for (long i = lo; i < hi; ++i) {
+      const double u = (coef ? g[i] * c : (double)g[i]) + w * p[i];
+      if (vel) {
+        vel[i] = (T)(momentum * vel[i] - s * u);
+        p[i] += vel[i];
+      } else {
+        p[i] -= (T)(s * u);
+      }
+      if (ema) ema[i] = (T)(decay * ema[i] + (1.0 - decay) * p[i]);
+    }
+  });
+}
+
 // ------------------------------------------------------------------ instantiations
 #define DCNN_CPU_INST(T)                                                                                             \
   template void elementwise<T>(int, int, const T*, const T*, T*, long, double, double);                             \
@@ -1621,7 +1722,11 @@ void ema_swap(T* a, T* b, long n) {
   template void adam_step_tail<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double, \
                                   int, const uint8_t*, const double*, T*, double);                                   \
   template void sgd_step_tail<T>(T*, const T*, T*, long, double, double, const double*, T*, double);                 \
-  template void ema_swap<T>(T*, T*, long);
+  template void ema_swap<T>(T*, T*, long);                                                                           \
+  template void lamb_step<T>(T*, const T*, T*, T*, long, double, double, double, double, double, double, double,     \
+                             const double*, T*, double, const int*, int, const int*, int, double*);                  \
+  template void lars_step<T>(T*, const T*, T*, long, double, double, double, double, double, const double*, T*,      \
+                             double, const int*, int, const int*, int, double*);
 
 DCNN_CPU_INST(float)
 DCNN_CPU_INST(double)

@@ -1,4 +1,5 @@
-"""Optimizers (reference `include/nn/optimizers.hpp:25-306`): SGD(+momentum), Adam, AdamW.
+"""Optimizers (reference `include/nn/optimizers.hpp:25-306`): SGD(+momentum), Adam, AdamW, and the
+layer-wise adaptive LAMB and LARS (``_Layerwise``: a trust ratio per parameter, two launches a step).
 
 ``attach(params, grads)`` as in the reference. When the attached tensors are exactly the views
 of one :class:`ParamArena` (the normal case: a Sequential or a pipeline stage), the update is
@@ -519,6 +520,248 @@ class AdamW(Adam):
                          ema_decay)
 
 
+class _Layerwise(Optimizer):
+    """What LAMB and LARS share: a trust ratio per parameter from the L2 norms of its weights and of
+    its update, taken on the weights before the step. On an arena the norms are ONE segmented
+    fixed-order reduction over the flat buffer (``ParamArena.segment_tables``; ``layerwise.hip`` on the
+    GPU, the native loops on the CPU) and the step is two launches; the trust table stays on the
+    device, so a captured step needs no host read. With ``no_decay_norm_bias`` a parameter flagged
+    ``no_decay`` (biases, norm affines, layer scales) takes ``wd = 0`` and trust 1. A zero norm gives
+    trust 1; a non-finite norm propagates into that parameter's step (no step is skipped)."""
+
+    layerwise = True  # TrainStep prewarms the "layerwise" ticket slot before a capture
+
+    def _init_layerwise(self, weight_decay, no_decay_norm_bias):
+        self.weight_decay = float(weight_decay)
+        self.no_decay_norm_bias = bool(no_decay_norm_bias)
+        self._tables = self._trust = self._part = None
+
+    def _attach_layerwise(self):
+        self._tables = self._trust = self._part = None
+        if self.no_decay_norm_bias and self.no_decay is None:
+            raise ValueError("no_decay_norm_bias needs to know which parameters are biases, norm affines or "
+                             "layer scales: attach a model or an arena, or pass no_decay=[...]")
+        if self.arena is not None:
+            self._tables = self.arena.segment_tables(self.no_decay_norm_bias)
+            if self._flat_p.is_cuda:
+                from ..ops import hip
+                self._trust, self._part = hip.layerwise_workspace(self._tables, self._flat_p.device)
+            else:
+                self._trust = torch.ones(max(3 * self._tables.nsegs, 1), dtype=torch.float64)
+        else:
+            self._trust = [1.0] * len(self.params)
+
+    def _excluded(self, i) -> bool:
+        return self.no_decay_norm_bias and self.no_decay[i]
+
+    def fused(self) -> bool:
+        return self.arena is not None and self._flat_p.is_cuda
+
+    def last_trust_ratios(self) -> List[float]:
+        """The trust ratio of every parameter in the last step (1.0 before the first), read on the
+        host: a device synchronisation on the GPU, so not for the hot path."""
+        if self._trust is None:
+            return []
+        if isinstance(self._trust, list):
+            return list(self._trust)
+        return [float(x) for x in self._trust[:self._tables.nsegs].double().cpu().tolist()]
+
+    def last_norm_sums(self) -> List[tuple]:
+        """``(sum p^2, sum u^2)`` per parameter as the last arena step's reduction left them (u: LAMB's
+        update ``r``, LARS's gradient before the clip coefficient): for inspection, a host read."""
+        if self._trust is None or isinstance(self._trust, list):
+            return []
+        ns = self._tables.nsegs
+        return [tuple(x) for x in self._trust[ns:3 * ns].double().cpu().reshape(ns, 2).tolist()]
+
+    @staticmethod
+    def _norm(t) -> float:
+        return math.sqrt(float((t.detach().double() ** 2).sum()))
+
+
+class LAMB(_Layerwise):
+    """LAMB (You et al. 2019): Adam's moments, the update ``r = (m / bc1) / (sqrt(v / bc2) + eps) +
+    wd p`` scaled per parameter by ``trust = ||p|| / ||r||``: ``p -= lr trust r``. State as Adam's
+    (``t``, ``m``, ``v``)."""
+
+    def __init__(self, learning_rate: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-6,
+                 weight_decay: float = 0.01, no_decay_norm_bias: bool = False, max_grad_norm: float = 0.0,
+                 ema_decay: float = 0.0):
+        super().__init__(learning_rate, max_grad_norm, ema_decay)
+        self._init_layerwise(weight_decay, no_decay_norm_bias)
+        self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
+        self.t = 0
+        self.m = self.v = None
+
+    def _on_attach(self):
+        if self.arena is not None:
+            self.m = [self.arena.new_zeros()]
+            self.v = [self.arena.new_zeros()]
+        else:
+            self.m = [torch.zeros_like(p) for p in self.params]
+            self.v = [torch.zeros_like(p) for p in self.params]
+        self.t = 0
+        self._attach_layerwise()
+
+    def prepare_step(self):
+        """As ``Adam.prepare_step``: the host counter advances, the device scalars are uploaded only
+        when stale and advance on the device (``lamb_scalars``: the bias corrections in double)."""
+        self.t += 1
+        self._bc = (1.0 - self.beta1 ** self.t, 1.0 - self.beta2 ** self.t)
+        if self.fused() and (self._hyper_dirty or self._hyper is None):
+            self._device_hyper([self.learning_rate, 0.0, 0.0, float(self.t - 1)])
+            self._hyper_dirty = False
+
+    def launch_step(self):
+        from ..ops import hip
+        from ..ops._ext import kernels, stream_ptr
+        kernels().lamb_scalars(self._hyper.data_ptr(), float(self.beta1), float(self.beta2),
+                               stream_ptr(self._flat_p.device))
+        bc1, bc2 = self._bc
+        hip.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate,
+                      self.beta1, self.beta2, self.epsilon, bc1, bc2, self.weight_decay, self._tables, self._trust,
+                      self._part, hyper=self._hyper, coef=self._launch_norm(), ema=self.ema[0] if self.ema else None,
+                      ema_decay=self.ema_decay)
+        self.arena.mark_synced()
+
+    def update(self):
+        if self.fused():
+            self.prepare_step()
+            self.launch_step()
+            return
+        self.t += 1
+        bc1 = 1.0 - self.beta1 ** self.t
+        bc2 = 1.0 - self.beta2 ** self.t
+        if self.arena is not None:
+            from ..ops import cpu   # native flat-buffer step (CPU arena, float32 or float64)
+            cpu.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1, self.beta2,
+                          self.epsilon, bc1, bc2, self.weight_decay, self._tables, self._trust, self._host_coef(),
+                          self.ema[0] if self.ema else None, self.ema_decay)
+            self.arena.sync_shadow()
+            return
+        coef = self._host_coef()  # over all parameters, before any of them is stepped
+        with torch.no_grad():
+            for i, (p, g) in enumerate(zip(self.params, self.grads)):
+                m, v = self.m[i], self.v[i]
+                if coef is not None:
+                    g = g * coef
+                m.mul_(self.beta1).add_((1 - self.beta1) * g)
+                v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
+                r = (m / bc1) / (torch.sqrt(v / bc2) + self.epsilon)
+                trust = 1.0
+                if not self._excluded(i):
+                    r = r + self.weight_decay * p
+                    pn, rn = self._norm(p), self._norm(r)
+                    trust = 1.0 if (pn == 0.0 or rn == 0.0) else pn / rn
+                self._trust[i] = trust
+                p.sub_(self.learning_rate * trust * r)
+                self._ema_torch(i, p)
+
+    def name(self):
+        return "LAMB"
+
+    def get_config(self):
+        return OptimizerConfig("lamb", "LAMB", dict(learning_rate=self.learning_rate, beta1=self.beta1,
+                                                    beta2=self.beta2, epsilon=self.epsilon,
+                                                    weight_decay=self.weight_decay,
+                                                    no_decay_norm_bias=self.no_decay_norm_bias,
+                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
+
+    def clone(self):
+        return LAMB(self.learning_rate, self.beta1, self.beta2, self.epsilon, self.weight_decay,
+                    self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
+
+    state_dict = Adam.state_dict
+    load_state_dict = Adam.load_state_dict
+
+
+class LARS(_Layerwise):
+    """LARS (You et al. 2017): momentum SGD with L2 weight decay, the step of every parameter scaled
+    by ``trust = tc ||p|| / (||g|| + wd ||p|| + eps)``: ``v = mom v - lr trust (g + wd p)``, ``p += v``
+    (the velocity convention of :class:`SGD`; momentum 0: no velocity buffer). State as SGD's."""
+
+    def __init__(self, learning_rate: float = 0.1, momentum: float = 0.9, weight_decay: float = 5e-4,
+                 trust_coefficient: float = 1e-3, epsilon: float = 1e-8, no_decay_norm_bias: bool = False,
+                 max_grad_norm: float = 0.0, ema_decay: float = 0.0):
+        super().__init__(learning_rate, max_grad_norm, ema_decay)
+        self._init_layerwise(weight_decay, no_decay_norm_bias)
+        self.momentum = float(momentum)
+        self.trust_coefficient, self.epsilon = float(trust_coefficient), float(epsilon)
+        self.velocity = None
+
+    def _on_attach(self):
+        self.velocity = None
+        if self.momentum > 0:
+            if self.arena is not None:
+                self.velocity = [self.arena.new_zeros()]
+            else:
+                self.velocity = [torch.zeros_like(p) for p in self.params]
+        self._attach_layerwise()
+
+    def prepare_step(self):
+        if self.fused() and (self._hyper_dirty or self._hyper is None):
+            self._device_hyper([self.learning_rate])
+            self._hyper_dirty = False
+
+    def launch_step(self):
+        from ..ops import hip
+        hip.lars_step(self._flat_p, self._flat_g, self.velocity[0] if self.momentum > 0 else None, self.arena.shadow,
+                      self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
+                      self._tables, self._trust, self._part, hyper=self._hyper, coef=self._launch_norm(),
+                      ema=self.ema[0] if self.ema else None, ema_decay=self.ema_decay)
+        self.arena.mark_synced()
+
+    def update(self):
+        if self.fused():
+            self.prepare_step()
+            self.launch_step()
+            return
+        if self.arena is not None:
+            from ..ops import cpu
+            cpu.lars_step(self._flat_p, self._flat_g, self.velocity[0] if self.momentum > 0 else None,
+                          self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
+                          self._tables, self._trust, self._host_coef(), self.ema[0] if self.ema else None,
+                          self.ema_decay)
+            self.arena.sync_shadow()
+            return
+        coef = self._host_coef()  # over all parameters, before any of them is stepped
+        with torch.no_grad():
+            for i, (p, g) in enumerate(zip(self.params, self.grads)):
+                if coef is not None:
+                    g = g * coef
+                trust, wd = 1.0, 0.0
+                if not self._excluded(i):
+                    wd = self.weight_decay
+                    pn, gn = self._norm(p), self._norm(g)
+                    if not (pn == 0.0 or gn == 0.0):
+                        trust = self.trust_coefficient * pn / (gn + wd * pn + self.epsilon)
+                self._trust[i] = trust
+                u = g + wd * p
+                if self.momentum > 0:
+                    self.velocity[i].mul_(self.momentum).sub_(self.learning_rate * trust * u)
+                    p.add_(self.velocity[i])
+                else:
+                    p.sub_(self.learning_rate * trust * u)
+                self._ema_torch(i, p)
+
+    def name(self):
+        return "LARS"
+
+    def get_config(self):
+        return OptimizerConfig("lars", "LARS", dict(learning_rate=self.learning_rate, momentum=self.momentum,
+                                                    weight_decay=self.weight_decay,
+                                                    trust_coefficient=self.trust_coefficient, epsilon=self.epsilon,
+                                                    no_decay_norm_bias=self.no_decay_norm_bias,
+                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
+
+    def clone(self):
+        return LARS(self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
+                    self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
+
+    state_dict = SGD.state_dict
+    load_state_dict = SGD.load_state_dict
+
+
 class OptimizerFactory:
     @staticmethod
     def create_from_config(config) -> Optimizer:
@@ -533,5 +776,13 @@ class OptimizerFactory:
             return Adam(p.get("learning_rate", 0.001), p.get("beta1", 0.9), p.get("beta2", 0.999),
                         p.get("epsilon", 1e-8), p.get("weight_decay", 0.0),
                         p.get("decouple_weight_decay", t == "adamw"), p.get("no_decay_norm_bias", False),
+                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
+        if t == "lamb":
+            return LAMB(p.get("learning_rate", 1e-3), p.get("beta1", 0.9), p.get("beta2", 0.999),
+                        p.get("epsilon", 1e-6), p.get("weight_decay", 0.01), p.get("no_decay_norm_bias", False),
+                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
+        if t == "lars":
+            return LARS(p.get("learning_rate", 0.1), p.get("momentum", 0.9), p.get("weight_decay", 5e-4),
+                        p.get("trust_coefficient", 1e-3), p.get("epsilon", 1e-8), p.get("no_decay_norm_bias", False),
                         p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
         raise ValueError(f"Unknown optimizer type: {t}")

@@ -40,6 +40,36 @@ def _strides(shape, channels_last):
     return tuple(reversed(st))
 
 
+class SegmentTables:
+    """The segment / chunk tables of the layer-wise optimizers (LAMB, LARS) for one flat buffer, built
+    by the kernel library's shared builder (``csrc/kernels/optim_segments.cpp``, the one the C++ front
+    end calls too). ``chunks`` int32 [nchunks, 3] = {first 64-element block, blocks, segment}: at most
+    4096 elements each, never across a parameter, in arena order. ``segs`` int32 [nsegs, 4] = {first
+    chunk, chunks, adapt, decay}. Host copies always; on a GPU device also static device copies, uploaded
+    once. ``cover``: the element the chunks reach (every buffer stepped holds at least that many)."""
+
+    def __init__(self, chunks, segs, cover: int, device):
+        self.chunks = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 3).contiguous()
+        self.segs = torch.tensor(segs, dtype=torch.int32).reshape(-1, 4).contiguous()
+        self.cover = int(cover)
+        self.nchunks, self.nsegs = self.chunks.shape[0], self.segs.shape[0]
+        self.device = torch.device(device)
+        gpu = self.device.type == "cuda"
+        self.chunks_dev = self.chunks.to(self.device) if gpu else None
+        self.segs_dev = self.segs.to(self.device) if gpu else None
+
+    @staticmethod
+    def from_slices(offsets, counts, no_decay, exclude: bool, n: int, device) -> "SegmentTables":
+        """``offsets`` / ``counts``: first element and element count of every slice in arena order;
+        ``no_decay``: one flag per slice (or None); ``exclude``: the optimizer's ``no_decay_norm_bias``
+        (a flagged slice then neither adapts nor decays); ``n``: the buffer's size."""
+        from ..ops._ext import kernels
+        flags = [int(bool(f)) for f in no_decay] if no_decay is not None else []
+        c, s, cover = kernels().optim_segments([int(o) for o in offsets], [int(k) for k in counts], flags,
+                                               bool(exclude), int(n))
+        return SegmentTables(c, s, cover, device)
+
+
 class ParamArena:
     def __init__(self, specs: List[ParamSpec], device: torch.device, shadow_dtype: Optional[torch.dtype] = None,
                  dtype: torch.dtype = torch.float32):
@@ -101,6 +131,23 @@ class ParamArena:
                 if s.no_decay:
                     host[lo // ALIGN:hi // ALIGN] = 1
             t = self._no_decay_blocks = host.to(self.device)
+        return t
+
+    def segment_tables(self, exclude: bool = False) -> SegmentTables:
+        """The layer-wise optimizers' tables for this arena: one segment per parameter. ``exclude``:
+        parameters flagged ``no_decay`` neither adapt nor decay. Built once per value and cached, like
+        :meth:`no_decay_blocks`: static memory a captured step replays as it is."""
+        cache = self.__dict__.setdefault("_segment_tables", {})
+        t = cache.get(bool(exclude))
+        if t is None:
+            counts = []
+            for s in self.specs:
+                n = 1
+                for d in s.shape:
+                    n *= d
+                counts.append(n)
+            t = cache[bool(exclude)] = SegmentTables.from_slices(self.offsets, counts, self.no_decay_flags(),
+                                                                 exclude, self.numel, self.device)
         return t
 
     def zero_grad(self):

@@ -539,6 +539,35 @@ def sgd_step_tail(p_, g, vel, lr, momentum, coef=None, ema=None, ema_decay=0.0):
                       coef is not None, float(coef if coef is not None else 1.0), p(ema), float(ema_decay))
 
 
+def _layerwise_args(who, n, tables, trust):
+    if tables.cover > n:
+        raise ValueError(f"{who}: the chunk table reaches element {tables.cover}, the buffers hold {n} "
+                         f"(chunks are whole 64-element blocks inside the buffers)")
+    if trust.dtype != torch.float64 or not trust.is_contiguous() or trust.numel() < 3 * tables.nsegs:
+        raise ValueError(f"{who}: trust is a float64 tensor of at least {3 * tables.nsegs} elements")
+    return (tables.chunks.data_ptr(), tables.nchunks, tables.segs.data_ptr(), tables.nsegs, trust.data_ptr())
+
+
+def lamb_step(p_, g, m, v, lr, b1, b2, eps, bc1, bc2, wd, tables, trust, coef=None, ema=None, ema_decay=0.0):
+    """One LAMB step over a flat float32 / float64 buffer, driven by the GPU's segment / chunk tables
+    (``SegmentTables``). ``trust`` (float64, ``[3 * nsegs]``) receives the trust ratios, then the pairs
+    ``{sum p^2, sum r^2}``. ``coef`` / ``ema`` as in :func:`adam_step_tail`."""
+    _same(p_, g, m, v, ema)
+    C().lamb_step(dt(p_), p_.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p_.numel(), float(lr), float(b1),
+                  float(b2), float(eps), float(bc1), float(bc2), float(wd), coef is not None,
+                  float(coef if coef is not None else 1.0), p(ema), float(ema_decay),
+                  *_layerwise_args("lamb_step", p_.numel(), tables, trust))
+
+
+def lars_step(p_, g, vel, lr, momentum, wd, trust_coefficient, eps, tables, trust, coef=None, ema=None,
+              ema_decay=0.0):
+    """One LARS step over a flat buffer (``vel`` None: no momentum); see :func:`lamb_step`."""
+    _same(p_, g, vel, ema)
+    C().lars_step(dt(p_), p_.data_ptr(), g.data_ptr(), p(vel), p_.numel(), float(lr), float(momentum), float(wd),
+                  float(trust_coefficient), float(eps), coef is not None, float(coef if coef is not None else 1.0),
+                  p(ema), float(ema_decay), *_layerwise_args("lars_step", p_.numel(), tables, trust))
+
+
 def ema_swap(a, b):
     """Exchange two flat buffers of one dtype and size in place; twice restores every bit."""
     _same(a, b)

@@ -396,6 +396,49 @@ def sgd_step_tail(p, g, vel, shadow, lr, momentum, hyper=None, coef=None, ema=No
                             ptr(hyper), ptr(coef), ptr(ema), float(ema_decay), stream_ptr(p.device))
 
 
+def layerwise_workspace(tables, device):
+    """``(trust, part)`` for :func:`lamb_step` / :func:`lars_step`: the trust table (``[3 * nsegs]``:
+    trust, then the pairs ``{sum p^2, sum u^2}``) and the per-chunk partial pairs (``[2 * nchunks]``)."""
+    return (torch.ones(max(3 * tables.nsegs, 1), dtype=F32, device=device),
+            torch.zeros(max(2 * tables.nchunks, 1), dtype=F32, device=device))
+
+
+def _layerwise_args(who, n, tables, trust, part, device):
+    if tables.chunks_dev is None or tables.chunks_dev.device != device:
+        raise ValueError(f"{who}: the segment tables live on {tables.device}, the buffers on {device}")
+    if tables.cover > n:
+        raise ValueError(f"{who}: the chunk table reaches element {tables.cover}, the buffers hold {n} "
+                         f"(chunks are whole 64-element blocks inside the buffers)")
+    for name, t, need in (("trust", trust, 3 * tables.nsegs), ("part", part, 2 * tables.nchunks)):
+        if t.dtype != F32 or not t.is_cuda or not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"{who}: {name} is a float32 GPU tensor of at least {need} elements")
+    tk = _ticket(device, 0, slot="layerwise")
+    return (tables.chunks_dev.data_ptr(), tables.nchunks, tables.segs_dev.data_ptr(), tables.nsegs, tables.cover,
+            part.data_ptr(), tk.data_ptr(), trust.data_ptr(), stream_ptr(device))
+
+
+def lamb_step(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, wd, tables, trust, part, hyper=None, coef=None,
+              ema=None, ema_decay=0.0):
+    """One LAMB step over a flat buffer: two launches on the current stream, no host sync, a fixed
+    summation order (bit-reproducible, eager or replayed). ``tables``: :class:`SegmentTables` on the
+    buffers' device; ``trust`` / ``part``: :func:`layerwise_workspace`. ``hyper`` (device ``{lr, bc1,
+    bc2}``), ``coef`` and ``ema`` are optional as in :func:`adam_step_tail`."""
+    n = _flat_f32("lamb_step", p, g, m, v, ema)
+    kernels().lamb_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(shadow), n, float(lr), float(b1),
+                        float(b2), float(eps), float(bc1), float(bc2), float(wd), ptr(hyper), ptr(coef), ptr(ema),
+                        float(ema_decay), *_layerwise_args("lamb_step", n, tables, trust, part, p.device))
+
+
+def lars_step(p, g, vel, shadow, lr, momentum, wd, trust_coefficient, eps, tables, trust, part, hyper=None,
+              coef=None, ema=None, ema_decay=0.0):
+    """One LARS step over a flat buffer (``vel`` None: no momentum); see :func:`lamb_step`. ``hyper``
+    is the device ``{lr}``."""
+    n = _flat_f32("lars_step", p, g, vel, ema)
+    kernels().lars_step(p.data_ptr(), g.data_ptr(), ptr(vel), ptr(shadow), n, float(lr), float(momentum), float(wd),
+                        float(trust_coefficient), float(eps), ptr(hyper), ptr(coef), ptr(ema), float(ema_decay),
+                        *_layerwise_args("lars_step", n, tables, trust, part, p.device))
+
+
 def ema_swap(a, b, shadow=None):
     """Exchange two flat fp32 buffers in one launch; ``shadow`` (bf16, optional) is refreshed from the
     new ``a``. Twice restores every bit."""

@@ -122,6 +122,8 @@ class TrainStep:
             with torch.cuda.stream(self._cap_stream):
                 # "gradnorm": the clipping norm's ticket (a slot an optimizer without clipping never uses)
                 slots = ("loss", "gradnorm") if getattr(self.opt, "max_grad_norm", 0.0) > 0.0 else ("loss",)
+                if getattr(self.opt, "layerwise", False):  # LAMB / LARS: the segmented norms' ticket
+                    slots += ("layerwise",)
                 hip.prewarm_tickets(self.model.device.torch_device, slots)
             torch.cuda.current_stream().wait_stream(self._cap_stream)
         return self._cap_stream

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ConvNeXt (7x7 depthwise conv, channel LayerNorm, 1x1 convs with GELU, layer scale; Liu et al.
 2022): ConvNeXt-pico on CIFAR-10 or, with ``--tiny``, ConvNeXt-T on Tiny-ImageNet-200: crop + flip +
-normalize, AdamW, softmax cross-entropy. ``--mixup A`` / ``--cutmix A`` / ``--label-smoothing E`` turn on the
+normalize, AdamW (``--opt lamb``: LAMB, the large-batch recipe's optimizer, same weight decay), softmax
+cross-entropy. ``--mixup A`` / ``--cutmix A`` / ``--label-smoothing E`` turn on the
 rest of the published recipe (0.8 / 1.0 / 0.1): batches are mixed on the device and the loss becomes
 ``soft_crossentropy``; ``--clip-grad N`` clips the global gradient norm inside the optimizer step and
 ``--model-ema D`` keeps an exponential moving average of the weights there (validation then runs on the
@@ -13,7 +14,7 @@ from common import loaders, parse, place
 
 from dcnn_amd.data import AugmentationBuilder, BatchMixer
 from dcnn_amd.models import INPUT_SHAPES, NUM_CLASSES, create_model
-from dcnn_amd.nn import AdamW, LossFactory, train_classification_model
+from dcnn_amd.nn import LAMB, AdamW, LossFactory, train_classification_model
 from dcnn_amd.utils import get_env
 
 STATS = {"cifar10": ((0.49139968, 0.48215827, 0.44653124), (0.24703233, 0.24348505, 0.26158768)),
@@ -25,8 +26,11 @@ def _args(ap):
     ap.add_argument("--steps", type=int, default=0, help="smoke mode: this many steps on synthetic data")
     ap.add_argument("--drop-path", type=float, default=0.0,
                     help="stochastic depth: the rate of the last block, rising linearly from 0 (ConvNeXt-T: 0.1)")
+    ap.add_argument("--opt", choices=["adamw", "lamb"], default="adamw",
+                    help="lamb: layer-wise trust ratios on Adam's update (large global batches)")
     ap.add_argument("--no-decay-norm-bias", action="store_true",
-                    help="keep biases, norm affines and layer scales out of AdamW's weight decay")
+                    help="keep biases, norm affines and layer scales out of the weight decay (LAMB: and out of "
+                         "the trust ratio)")
     ap.add_argument("--mixup", type=float, default=None, help="Mixup alpha (ConvNeXt: 0.8); default MIXUP_ALPHA or 0")
     ap.add_argument("--cutmix", type=float, default=None, help="CutMix alpha (ConvNeXt: 1.0); default CUTMIX_ALPHA or 0")
     ap.add_argument("--label-smoothing", type=float, default=None,
@@ -52,8 +56,12 @@ soft = cfg.mixup_alpha > 0 or cfg.cutmix_alpha > 0 or cfg.label_smoothing > 0
 kind = "tiny" if a.tiny else "cifar10"
 name = "convnext_tiny_tiny_imagenet" if a.tiny else "convnext_pico_cifar10"
 model = place(create_model(name, drop_path_rate=a.drop_path), a)
-opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05, no_decay_norm_bias=a.no_decay_norm_bias,
-            max_grad_norm=cfg.max_grad_norm, ema_decay=cfg.ema_decay)
+if a.opt == "lamb":
+    opt = LAMB(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-6, 0.05, no_decay_norm_bias=a.no_decay_norm_bias,
+               max_grad_norm=cfg.max_grad_norm, ema_decay=cfg.ema_decay)
+else:
+    opt = AdamW(get_env("LR_INITIAL", 0.001), 0.9, 0.999, 1e-8, 0.05, no_decay_norm_bias=a.no_decay_norm_bias,
+                max_grad_norm=cfg.max_grad_norm, ema_decay=cfg.ema_decay)
 loss_fn = LossFactory.create("soft_crossentropy", label_smoothing=cfg.label_smoothing) if soft else \
     LossFactory.create("softmax_crossentropy")
 if a.steps > 0:
@@ -74,6 +82,9 @@ if a.steps > 0:
         opt.update()
         losses.append(float(loss))
     print(f"{name}: {model.num_parameters()} parameters, batch {n}, losses " + " ".join(f"{v:.4f}" for v in losses))
+    if a.opt == "lamb":
+        tr = opt.last_trust_ratios()
+        print(f"last trust ratios: min {min(tr):.4f} max {max(tr):.4f} over {len(tr)} parameters")
     if opt.max_grad_norm > 0:
         print(f"last gradient norm {opt.last_grad_norm():.4f} (clipped at {opt.max_grad_norm})")
     if opt.ema is not None:

@@ -17,8 +17,10 @@
 //                                              one stride-2 basic residual block, forward + backward on
 //                                              fixed data; its input gradient and parameter gradients
 //   host_api_parity train <model_name> <steps> <batch> <save> [--device GPU] [--graph] [--adamw-no-decay]
-//                         [--mix] [--switch-to-labels] [--clip-ema MAX_NORM]
+//                         [--mix] [--switch-to-labels] [--clip-ema MAX_NORM] [--opt lamb|lars]
 //                                              Adam steps on a synthetic set, then save
+//                                              (--opt lamb|lars: LAMB / LARS steps instead, the trust
+//                                              ratios of the last step printed; dumps as --clip-ema)
 //                                              (--clip-ema: global-norm clipping at MAX_NORM and a
 //                                              weight EMA of decay 0.9; the EMA weights are saved
 //                                              too, as <save>.ema, and the last gradient norm printed;
@@ -33,6 +35,8 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <memory>
+#include <stdexcept>
 #include <string>
 
 #include "dcnn/nn.hpp"
@@ -360,11 +364,35 @@ int main(int argc, char** argv) {
       SyntheticClassification data((size_t)batch * steps, 3, hw, hw, classes, 5, 0.3f);
       // --adamw-no-decay: AdamW, weight decay 0.1, biases / norm affines / layer scales excluded
       const bool nd = flag_arg(argc, argv, "--adamw-no-decay");
-      Adam opt(1e-3f, 0.9f, 0.999f, 1e-8f, nd ? 0.1f : 0.f, nd);
-      opt.set_no_decay_norm_bias(nd);
+      // --opt lamb|lars: the layer-wise optimizers, biases / norm affines / layer scales excluded
+      // (LAMB lr 1e-3, weight decay 0.1; LARS lr 0.5, momentum 0.9, weight decay 0.01, tc 0.02)
+      std::string oname;
       float clip = 0.f;
-      for (int i = 1; i + 1 < argc; ++i)
+      for (int i = 1; i + 1 < argc; ++i) {
         if (std::string(argv[i]) == "--clip-ema") clip = (float)std::atof(argv[i + 1]);
+        if (std::string(argv[i]) == "--opt") oname = argv[i + 1];
+      }
+      std::unique_ptr<Optimizer> optp;
+      LayerwiseState* lw = nullptr;
+      if (oname == "lamb") {
+        auto o = std::make_unique<LAMB>(1e-3f, 0.9, 0.999, 1e-6f, 0.1f);
+        o->set_no_decay_norm_bias(true);
+        lw = o.get();
+        optp = std::move(o);
+      } else if (oname == "lars") {
+        auto o = std::make_unique<LARS>(0.5f, 0.9f, 0.01f, 0.02f, 1e-8f);
+        o->set_no_decay_norm_bias(true);
+        lw = o.get();
+        optp = std::move(o);
+      } else if (oname.empty() || oname == "adam") {
+        auto o = std::make_unique<Adam>(1e-3f, 0.9f, 0.999f, 1e-8f, nd ? 0.1f : 0.f, nd);
+        o->set_no_decay_norm_bias(nd);
+        optp = std::move(o);
+      } else {
+        throw std::invalid_argument("--opt " + oname + ": adam, lamb or lars");
+      }
+      Optimizer& opt = *optp;
+      const bool dump = clip > 0.f || lw != nullptr;  // the initial model and every batch, for a replay elsewhere
       if (clip > 0.f) {
         opt.set_max_grad_norm(clip);
         opt.set_ema_decay(0.9f);
@@ -380,10 +408,10 @@ int main(int argc, char** argv) {
       bool graph = false;  // --graph: the GPU step captured once (TrainGraph) and replayed
       for (int i = 1; i < argc; ++i) graph = graph || std::string(argv[i]) == "--graph";
       TrainGraph tg(m, opt, loss);
-      if (clip > 0.f) m.save_to_file(std::string(argv[5]) + ".init");
+      if (dump) m.save_to_file(std::string(argv[5]) + ".init");
       std::printf("losses");
       for (int i = 0; i < steps && data.next(batch, x, y); ++i) {
-        if (clip > 0.f) {
+        if (dump) {
           const std::string pre = std::string(argv[5]) + ".";
           std::ofstream fx(pre + "x" + std::to_string(i) + ".bin", std::ios::binary);
           x.to(Device::cpu()).save(fx);
@@ -398,7 +426,7 @@ int main(int argc, char** argv) {
           x = xd;
           y = t;
         }
-        if (graph && (dev.is_gpu() || clip > 0.f)) {
+        if (graph && (dev.is_gpu() || dump)) {
           const double l = tg.step(x, y);
           std::printf(" %.6g", dev.is_gpu() ? tg.last_loss() : l);
           continue;
@@ -411,6 +439,11 @@ int main(int argc, char** argv) {
       }
       std::printf("\n");
       m.save_to_file(argv[5]);
+      if (lw != nullptr) {
+        std::printf("trust");
+        for (float t : lw->last_trust_ratios()) std::printf(" %.9g", (double)t);
+        std::printf("\n");
+      }
       if (clip > 0.f) {
         std::printf("grad_norm %.9g\n", (double)opt.last_grad_norm());
         opt.swap_ema(m.parameters());
