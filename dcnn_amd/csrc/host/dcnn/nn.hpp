@@ -715,6 +715,10 @@ class Optimizer {
   // not averaged. 0 = off.
   void set_ema_decay(float decay);
   float ema_decay() const { return ema_decay_; }
+  // Adam, LAMB and LARS: biases, norm affines and layer scales (Param::no_decay) take the step
+  // without weight decay (LAMB and LARS: and with trust 1)
+  void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
+  bool no_decay_norm_bias() const { return no_decay_; }
   // create what the switches need (EMA buffers, the norm block, the reduction's workspace) now;
   // step() does it on demand, a graph capture needs it done before
   void prepare(const std::vector<Param*>& params);
@@ -726,23 +730,40 @@ class Optimizer {
   // What TrainGraph asks of an optimizer whose step it captures: the step reads its scalars (learning
   // rate, step count) from device memory. step_count / set_step_count: the host mirror of the device
   // counter; before_replay: a replay is about to run one step on the device (mirror it, upload a
-  // changed learning rate); upload_hyper: host state -> device scalars, outside a capture.
+  // changed learning rate); upload_hyper: host state -> device scalars, outside a capture. The count
+  // of an optimizer that does not count its steps (SGD, LARS) stays 0.
   virtual bool capturable() const { return false; }
-  virtual long step_count() const { return 0; }
-  virtual void set_step_count(long t) { (void)t; }
-  virtual void before_replay() {}
-  virtual void upload_hyper() {}
+  virtual long step_count() const { return t_; }
+  virtual void set_step_count(long t) { t_ = t; }
+  virtual void before_replay();
+  virtual void upload_hyper();
 
  protected:
   bool tail() const { return max_norm_ > 0.f || ema_decay_ > 0.f; }
   // GPU arena: launch the norm reduction, return the device pointer to coef (null with clipping off)
   const float* launch_norm(ParamArena* a);
-  // per-parameter path: the coefficient from the norm over all parameters (false with clipping off)
-  bool host_coef(const std::vector<Param*>& params, double* coef);
+  // per-parameter path: the coefficient from the norm over all parameters (null with clipping off)
+  const double* host_coef(const std::vector<Param*>& params);
+  // the EMA buffer of an arena or of a parameter, null with the EMA off
+  template <class Owner>
+  float* ema_of(Owner* x) const {
+    return ema_decay_ > 0.f ? x->ema.template ptr<float>() : nullptr;
+  }
+  // GPU arena path of a capturable step: create the device scalars, bring them up to date with the
+  // host (lr, t), and throw "<what> changed inside a graph capture" if that has to happen in one
+  void sync_hyper(ParamArena* a, const char* what);
   float lr_;
   float max_norm_ = 0.f, ema_decay_ = 0.f;
+  bool no_decay_ = false;
+  long t_ = 0;
   Tensor norm_;                      // device {sumsq, norm, coef, max_norm} (GPU arena path)
   float host_norm_ = std::nanf("");  // per-parameter path
+  double host_coef_ = 1.0;
+  // step scalars in device memory {lr, bc1, bc2, t} (t and the bias corrections advance on the
+  // device) and what the host last uploaded
+  Tensor hyper_;
+  float hyper_lr_ = -1.f;
+  long hyper_t_ = -1;
 };
 
 class SGD : public Optimizer {
@@ -761,28 +782,15 @@ class Adam : public Optimizer {
                 bool decoupled = false)
       : Optimizer(lr), b1_(b1), b2_(b2), eps_(eps), wd_(wd), decoupled_(decoupled) {}
   void step(const std::vector<Param*>& params) override;
-  // biases, norm affines and layer scales (Param::no_decay) take the step without weight decay; on
-  // the GPU arena path through the arena's block table and a second instance of the fused kernel
-  void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
-  bool no_decay_norm_bias() const { return no_decay_; }
+  // (no_decay_norm_bias on the GPU arena path: the arena's block table and a second instance of the
+  // fused kernel)
   bool capturable() const override { return true; }
-  long step_count() const override { return t_; }
-  void set_step_count(long t) override { t_ = t; }
-  // a replayed graph ran one step on the device: mirror it on the host (t) and upload a changed
-  // learning rate before the replay
+  // a replayed graph runs one step on the device: mirror its count on the host
   void before_replay() override;
-  // host step state (lr, t) -> the device step scalars (outside a capture)
-  void upload_hyper() override;
 
  protected:
   float b1_, b2_, eps_, wd_;
   bool decoupled_;
-  bool no_decay_ = false;
-  long t_ = 0;
-  // GPU arena path: step scalars in device memory {lr, bc1, bc2, t}, updated on the device
-  Tensor hyper_;
-  float hyper_lr_ = -1.f;
-  long hyper_t_ = -1;
 };
 
 // What LAMB and LARS share: a trust ratio per parameter from the L2 norms of its weights and of its
@@ -804,6 +812,10 @@ class LayerwiseState {
     std::vector<int> chunks, segs;
   };
   static One one_segment(long n, bool adapt);
+  // the per-parameter CPU step of `who`: step_one(p, chunks, nchunks, segs, out) makes the cpu_ops
+  // call for parameter p as one segment, out[0] becomes its trust ratio
+  template <class StepOne>
+  void step_each(const std::vector<Param*>& params, const char* who, bool no_decay, StepOne step_one);
   Tensor part_, out_;           // GPU arena path
   size_t nsegs_ = 0;
   std::vector<double> trust_;   // per-parameter path
@@ -830,17 +842,10 @@ class LARS : public SGD, public LayerwiseState {
                 float eps = 1e-8f)
       : SGD(lr, momentum), wd_(wd), tc_(trust_coefficient), eps_(eps) {}
   void step(const std::vector<Param*>& params) override;
-  void set_no_decay_norm_bias(bool on) { no_decay_ = on; }
-  bool no_decay_norm_bias() const { return no_decay_; }
   bool capturable() const override { return true; }
-  void before_replay() override;
-  void upload_hyper() override;
 
  private:
   float wd_, tc_, eps_;
-  bool no_decay_ = false;
-  Tensor hyper_;  // GPU arena path: {lr} in device memory
-  float hyper_lr_ = -1.f;
 };
 
 

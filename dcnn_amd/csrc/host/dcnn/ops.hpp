@@ -77,13 +77,11 @@ void relu_mask(const float* dy, const float* y, float* dx, long n);
 void adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float bc1,
           float bc2, float wd, bool decoupled);
 void sgd(float* p, const float* g, float* vel, long n, float lr, float momentum);
-// adam with a weight-decay exclusion: nodecay[(n + 63) / 64], a set byte steps its 64-element block
-// with wd = 0 (a parameter smaller than 64 elements: one byte)
-void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                  float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
 // global-norm clipping and weight EMA: the sum of g^2 (fixed order, double partials), and the steps
-// with optional inputs, null = off: nodecay (as above), coef (the step takes g * coef and leaves g as
-// it is), ema (ema = decay ema + (1 - decay) p_new); ema_swap exchanges two buffers
+// with optional inputs, null = off: nodecay (the weight-decay exclusion: nodecay[(n + 63) / 64], a set
+// byte steps its 64-element block with wd = 0; a parameter smaller than 64 elements: one byte), coef
+// (the step takes g * coef and leaves g as it is), ema (ema = decay ema + (1 - decay) p_new);
+// ema_swap exchanges two buffers
 double grad_sumsq(const float* g, long n);
 void adam_tail(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float bc1,
                float bc2, float wd, bool decoupled, const uint8_t* nodecay, const double* coef, float* ema,
@@ -343,13 +341,10 @@ void sgd(float* p, const float* g, float* vel, void* shadow, long n, float lr, f
 // device-resident Adam step scalars hyper = {lr, bc1, bc2, t} (a captured step replays with the
 // current values): t += 1 and the bias corrections on the device, then the fused update reading them
 void adam_hyper_step(float* hyper, float b1, float b2);
+// nodecay (optional): the weight-decay exclusion, a device table of one byte per 64-element block,
+// read by a second instance of the kernel; null launches the plain one
 void adam_dev(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2, float eps,
-              float wd, bool decoupled, const float* hyper);
-// the same with the weight-decay exclusion: nodecay is a device table of one byte per 64-element block
-void adam_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
-                  float eps, float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay);
-void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2,
-                      float eps, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay);
+              float wd, bool decoupled, const float* hyper, const uint8_t* nodecay);
 // global-norm clipping and weight EMA (loss_optim.hip). grad_norm_workspace: the per-workgroup
 // partials and the self-resetting ticket word of grad_sumsq for n elements, created and zeroed
 // outside any capture. grad_sumsq: out[4] = {sumsq, norm, coef, max_norm} on the device, one launch,

@@ -2284,6 +2284,12 @@ ParamArena* whole_arena(const std::vector<Param*>& params) {
     if (p->arena.get() != a) return nullptr;
   return a;
 }
+
+// per-parameter path: a state tensor of p (moment, velocity), created with zeros on first use
+float* state_of(const Param* p, Tensor& state) {
+  if (!state.defined()) state = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
+  return state.ptr<float>();
+}
 }  // namespace
 
 void Optimizer::set_max_grad_norm(float max_norm) {
@@ -2321,14 +2327,37 @@ const float* Optimizer::launch_norm(ParamArena* a) {
   return norm_.ptr<float>() + 2;
 }
 
-bool Optimizer::host_coef(const std::vector<Param*>& params, double* coef) {
-  if (!(max_norm_ > 0.f)) return false;
+const double* Optimizer::host_coef(const std::vector<Param*>& params) {
+  if (!(max_norm_ > 0.f)) return nullptr;
   double sumsq = 0.0;  // over all parameters, before any of them is stepped
   for (auto* p : params) sumsq += cpu_ops::grad_sumsq(p->grad.ptr<float>(), p->value.numel());
   const double norm = std::sqrt(sumsq), c = max_norm_ / (norm + 1e-6);
   host_norm_ = (float)norm;
-  *coef = c < 1.0 || c != c ? c : 1.0;
-  return true;
+  host_coef_ = c < 1.0 || c != c ? c : 1.0;
+  return &host_coef_;
+}
+
+void Optimizer::upload_hyper() {
+  if (!hyper_.defined()) return;
+  const float h[4] = {lr_, 0.f, 0.f, (float)t_};  // bc1 / bc2 are recomputed by the next step
+  gpu::copy(hyper_.data(), h, sizeof h, 0);
+  hyper_lr_ = lr_;
+  hyper_t_ = t_;
+}
+
+void Optimizer::before_replay() {
+  if (hyper_.defined() && hyper_lr_ != lr_) {
+    gpu::copy(hyper_.data(), &lr_, sizeof lr_, 0);
+    hyper_lr_ = lr_;
+  }
+}
+
+void Optimizer::sync_hyper(ParamArena* a, const char* what) {
+  if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
+  if (hyper_lr_ != lr_ || hyper_t_ != t_) {
+    if (gpu::Graph::capturing()) throw std::runtime_error(std::string(what) + " changed inside a graph capture");
+    upload_hyper();
+  }
 }
 
 float Optimizer::last_grad_norm() const {
@@ -2357,21 +2386,19 @@ void SGD::step(const std::vector<Param*>& params) {
     float* vel = momentum_ != 0.f ? a->m.ptr<float>() : nullptr;
     if (tail())
       gpu_ops::sgd_tail(a->value.ptr<float>(), a->grad.ptr<float>(), vel, a->shadow.data(), (long)a->n, lr_, momentum_,
-                        launch_norm(a), ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_);
+                        launch_norm(a), ema_of(a), ema_decay_);
     else
       gpu_ops::sgd(a->value.ptr<float>(), a->grad.ptr<float>(), vel, a->shadow.data(), (long)a->n, lr_, momentum_);
     a->refresh_transposes();
     return;
   }
-  double coef = 1.0;
-  const bool clip = host_coef(params, &coef);
+  const double* coef = host_coef(params);
   for (auto* p : params) {
     if (p->arena) p->arena->wt_valid = false;  // (the convs transpose their own operand)
-    if (momentum_ != 0.f && !p->m.defined()) p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-    float* vel = momentum_ != 0.f ? p->m.ptr<float>() : nullptr;
+    float* vel = momentum_ != 0.f ? state_of(p, p->m) : nullptr;
     if (tail())  // (CPU parameters: prepare() refused any other)
-      cpu_ops::sgd_tail(p->value.ptr<float>(), p->grad.ptr<float>(), vel, p->value.numel(), lr_, momentum_,
-                        clip ? &coef : nullptr, ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_);
+      cpu_ops::sgd_tail(p->value.ptr<float>(), p->grad.ptr<float>(), vel, p->value.numel(), lr_, momentum_, coef,
+                        ema_of(p), ema_decay_);
     else if (p->value.device().is_gpu())
       gpu_ops::sgd(p->value.ptr<float>(), p->grad.ptr<float>(), vel, p->shadow.data(), p->value.numel(), lr_,
                    momentum_);
@@ -2380,19 +2407,8 @@ void SGD::step(const std::vector<Param*>& params) {
   }
 }
 
-void Adam::upload_hyper() {
-  if (!hyper_.defined()) return;
-  const float h[4] = {lr_, 0.f, 0.f, (float)t_};  // bc1 / bc2 are recomputed by the next step
-  gpu::copy(hyper_.data(), h, sizeof h, 0);
-  hyper_lr_ = lr_;
-  hyper_t_ = t_;
-}
-
 void Adam::before_replay() {
-  if (hyper_.defined() && hyper_lr_ != lr_) {
-    gpu::copy(hyper_.data(), &lr_, sizeof lr_, 0);
-    hyper_lr_ = lr_;
-  }
+  Optimizer::before_replay();
   ++t_;
   ++hyper_t_;
 }
@@ -2401,50 +2417,37 @@ void Adam::step(const std::vector<Param*>& params) {
   if (tail()) prepare(params);
   if (ParamArena* a = whole_arena(params)) {
     // step scalars on the device (a captured step replays with the current lr and t)
-    if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
-    if (hyper_lr_ != lr_ || hyper_t_ != t_) {
-      if (gpu::Graph::capturing()) throw std::runtime_error("Adam: step scalars changed inside a graph capture");
-      upload_hyper();
-    }
+    sync_hyper(a, "Adam: step scalars");
     ++t_;
     ++hyper_t_;
     gpu_ops::adam_hyper_step(hyper_.ptr<float>(), b1_, b2_);
+    const uint8_t* nodecay = no_decay_ ? static_cast<const uint8_t*>(a->nodecay.data()) : nullptr;
     if (tail())
       gpu_ops::adam_tail(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
                          a->shadow.data(), (long)a->n, 0.f, b1_, b2_, eps_, 1.f, 1.f, wd_, decoupled_,
-                         hyper_.ptr<float>(), no_decay_ ? static_cast<const uint8_t*>(a->nodecay.data()) : nullptr,
-                         launch_norm(a), ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_);
-    else if (no_decay_)
-      gpu_ops::adam_dev_nodecay(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
-                                a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>(),
-                                static_cast<const uint8_t*>(a->nodecay.data()));
+                         hyper_.ptr<float>(), nodecay, launch_norm(a), ema_of(a), ema_decay_);
     else
       gpu_ops::adam_dev(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(),
-                        a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>());
+                        a->shadow.data(), (long)a->n, b1_, b2_, eps_, wd_, decoupled_, hyper_.ptr<float>(), nodecay);
     a->refresh_transposes();
     return;
   }
   ++t_;
   const float bc1 = 1.f - std::pow(b1_, (float)t_), bc2 = 1.f - std::pow(b2_, (float)t_);
-  double coef = 1.0;
-  const bool clip = host_coef(params, &coef);
+  const double* coef = host_coef(params);
   for (auto* p : params) {
     if (p->arena) p->arena->wt_valid = false;
-    if (!p->m.defined()) {
-      p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-      p->v = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-    }
+    float *m = state_of(p, p->m), *v = state_of(p, p->v);
     const float wd = no_decay_ && p->no_decay ? 0.f : wd_;  // (per parameter: the flag itself, no table)
     if (tail())  // (CPU parameters: prepare() refused any other)
-      cpu_ops::adam_tail(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                         p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_, nullptr,
-                         clip ? &coef : nullptr, ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_);
+      cpu_ops::adam_tail(p->value.ptr<float>(), p->grad.ptr<float>(), m, v, p->value.numel(), lr_, b1_, b2_, eps_, bc1,
+                         bc2, wd, decoupled_, nullptr, coef, ema_of(p), ema_decay_);
     else if (p->value.device().is_gpu())
-      gpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                    p->shadow.data(), p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
+      gpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), m, v, p->shadow.data(), p->value.numel(), lr_, b1_,
+                    b2_, eps_, bc1, bc2, wd, decoupled_);
     else
-      cpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                    p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2, wd, decoupled_);
+      cpu_ops::adam(p->value.ptr<float>(), p->grad.ptr<float>(), m, v, p->value.numel(), lr_, b1_, b2_, eps_, bc1, bc2,
+                    wd, decoupled_);
   }
 }
 
@@ -2476,96 +2479,67 @@ std::vector<float> LayerwiseState::last_trust_ratios() const {
   return h;
 }
 
+template <class StepOne>
+void LayerwiseState::step_each(const std::vector<Param*>& params, const char* who, bool no_decay, StepOne step_one) {
+  trust_.assign(params.size(), 1.0);
+  for (size_t i = 0; i < params.size(); ++i) {
+    Param* p = params[i];
+    if (p->value.device().is_gpu())
+      throw std::runtime_error(std::string(who) + " on the GPU needs all parameters of one arena");
+    const One o = one_segment((long)p->value.numel(), !(no_decay && p->no_decay));
+    double out[3] = {1.0, 0.0, 0.0};
+    step_one(p, o.chunks.data(), (int)o.chunks.size() / 3, o.segs.data(), out);
+    trust_[i] = out[0];
+  }
+}
+
 void LAMB::step(const std::vector<Param*>& params) {
-  if (tail()) prepare(params);
+  if (tail()) prepare(params);  // (the per-parameter path: creates every parameter's EMA too)
   if (ParamArena* a = whole_arena(params)) {
     workspace(a);
-    if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
-    if (hyper_lr_ != lr_ || hyper_t_ != t_) {
-      if (gpu::Graph::capturing()) throw std::runtime_error("LAMB: step scalars changed inside a graph capture");
-      upload_hyper();
-    }
+    sync_hyper(a, "LAMB: step scalars");
     ++t_;
     ++hyper_t_;
     gpu_ops::lamb_scalars(hyper_.ptr<float>(), b1d_, b2d_);
     const OptimSegments& t = *a->segments[no_decay_ ? 1 : 0];
     gpu_ops::lamb(a->value.ptr<float>(), a->grad.ptr<float>(), a->m.ptr<float>(), a->v.ptr<float>(), a->shadow.data(),
-                  (long)a->n, lr_, b1d_, b2d_, eps_, 1.f, 1.f, wd_, hyper_.ptr<float>(), launch_norm(a),
-                  ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_, a->seg_chunks.data(),
-                  (int)t.chunks.size(), a->seg_info[no_decay_ ? 1 : 0].data(), (int)t.segs.size(), t.cover,
-                  part_.ptr<float>(), out_.ptr<float>());
+                  (long)a->n, lr_, b1d_, b2d_, eps_, 1.f, 1.f, wd_, hyper_.ptr<float>(), launch_norm(a), ema_of(a),
+                  ema_decay_, a->seg_chunks.data(), (int)t.chunks.size(), a->seg_info[no_decay_ ? 1 : 0].data(),
+                  (int)t.segs.size(), t.cover, part_.ptr<float>(), out_.ptr<float>());
     a->refresh_transposes();
     return;
   }
   ++t_;
   const double bc1 = 1.0 - std::pow(b1d_, (double)t_), bc2 = 1.0 - std::pow(b2d_, (double)t_);
-  double coef = 1.0;
-  const bool clip = host_coef(params, &coef);
-  trust_.assign(params.size(), 1.0);
-  for (size_t i = 0; i < params.size(); ++i) {
-    Param* p = params[i];
-    if (p->value.device().is_gpu()) throw std::runtime_error("LAMB on the GPU needs all parameters of one arena");
-    if (!p->m.defined()) {
-      p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-      p->v = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-    }
-    if (ema_decay_ > 0.f && !p->ema.defined()) p->ema = p->value.clone();
-    const One o = one_segment((long)p->value.numel(), !(no_decay_ && p->no_decay));
-    double out[3] = {1.0, 0.0, 0.0};
-    cpu_ops::lamb(p->value.ptr<float>(), p->grad.ptr<float>(), p->m.ptr<float>(), p->v.ptr<float>(),
-                  (long)p->value.numel(), lr_, b1d_, b2d_, eps_, bc1, bc2, wd_, clip ? &coef : nullptr,
-                  ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_, o.chunks.data(),
-                  (int)o.chunks.size() / 3, o.segs.data(), 1, out);
-    trust_[i] = out[0];
-  }
-}
-
-void LARS::upload_hyper() {
-  if (!hyper_.defined()) return;
-  const float h[4] = {lr_, 0.f, 0.f, 0.f};
-  gpu::copy(hyper_.data(), h, sizeof h, 0);
-  hyper_lr_ = lr_;
-}
-
-void LARS::before_replay() {
-  if (hyper_.defined() && hyper_lr_ != lr_) upload_hyper();
+  const double* coef = host_coef(params);
+  step_each(params, "LAMB", no_decay_, [&](Param* p, const int* chunks, int nchunks, const int* segs, double* out) {
+    float *m = state_of(p, p->m), *v = state_of(p, p->v);
+    cpu_ops::lamb(p->value.ptr<float>(), p->grad.ptr<float>(), m, v, (long)p->value.numel(), lr_, b1d_, b2d_, eps_,
+                  bc1, bc2, wd_, coef, ema_of(p), ema_decay_, chunks, nchunks, segs, 1, out);
+  });
 }
 
 void LARS::step(const std::vector<Param*>& params) {
-  if (tail()) prepare(params);
+  if (tail()) prepare(params);  // (the per-parameter path: creates every parameter's EMA too)
   const float mom = momentum();
   if (ParamArena* a = whole_arena(params)) {
     workspace(a);
-    if (!hyper_.defined()) hyper_ = Tensor::zeros({4}, DType::F32, a->value.device());
-    if (hyper_lr_ != lr_) {
-      if (gpu::Graph::capturing()) throw std::runtime_error("LARS: the learning rate changed inside a graph capture");
-      upload_hyper();
-    }
+    sync_hyper(a, "LARS: the learning rate");
     const OptimSegments& t = *a->segments[no_decay_ ? 1 : 0];
     gpu_ops::lars(a->value.ptr<float>(), a->grad.ptr<float>(), mom != 0.f ? a->m.ptr<float>() : nullptr,
                   a->shadow.data(), (long)a->n, lr_, mom, wd_, tc_, eps_, hyper_.ptr<float>(), launch_norm(a),
-                  ema_decay_ > 0.f ? a->ema.ptr<float>() : nullptr, ema_decay_, a->seg_chunks.data(),
-                  (int)t.chunks.size(), a->seg_info[no_decay_ ? 1 : 0].data(), (int)t.segs.size(), t.cover,
-                  part_.ptr<float>(), out_.ptr<float>());
+                  ema_of(a), ema_decay_, a->seg_chunks.data(), (int)t.chunks.size(),
+                  a->seg_info[no_decay_ ? 1 : 0].data(), (int)t.segs.size(), t.cover, part_.ptr<float>(),
+                  out_.ptr<float>());
     a->refresh_transposes();
     return;
   }
-  double coef = 1.0;
-  const bool clip = host_coef(params, &coef);
-  trust_.assign(params.size(), 1.0);
-  for (size_t i = 0; i < params.size(); ++i) {
-    Param* p = params[i];
-    if (p->value.device().is_gpu()) throw std::runtime_error("LARS on the GPU needs all parameters of one arena");
-    if (mom != 0.f && !p->m.defined()) p->m = Tensor::zeros(p->value.shape(), DType::F32, p->value.device());
-    if (ema_decay_ > 0.f && !p->ema.defined()) p->ema = p->value.clone();
-    const One o = one_segment((long)p->value.numel(), !(no_decay_ && p->no_decay));
-    double out[3] = {1.0, 0.0, 0.0};
-    cpu_ops::lars(p->value.ptr<float>(), p->grad.ptr<float>(), mom != 0.f ? p->m.ptr<float>() : nullptr,
-                  (long)p->value.numel(), lr_, mom, wd_, tc_, eps_, clip ? &coef : nullptr,
-                  ema_decay_ > 0.f ? p->ema.ptr<float>() : nullptr, ema_decay_, o.chunks.data(),
-                  (int)o.chunks.size() / 3, o.segs.data(), 1, out);
-    trust_[i] = out[0];
-  }
+  const double* coef = host_coef(params);
+  step_each(params, "LARS", no_decay_, [&](Param* p, const int* chunks, int nchunks, const int* segs, double* out) {
+    cpu_ops::lars(p->value.ptr<float>(), p->grad.ptr<float>(), mom != 0.f ? state_of(p, p->m) : nullptr,
+                  (long)p->value.numel(), lr_, mom, wd_, tc_, eps_, coef, ema_of(p), ema_decay_, chunks, nchunks, segs,
+                  1, out);
+  });
 }
 
 // ------------------------------------------------------------------ data

@@ -157,11 +157,6 @@ void adam(float* p, const float* g, float* m, float* v, long n, float lr, float 
   C::adam_step(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0);
 }
 
-void adam_nodecay(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                  float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay) {
-  C::adam_step_nodecay(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nodecay);
-}
-
 void drop_path_mask(float* mask, long N, float p, uint64_t seed, uint64_t draw) {
   C::drop_path_mask(mask, N, p, seed, draw);
 }

@@ -1227,23 +1227,16 @@ void adam(float* p, const float* g, float* m, float* v, void* shadow, long n, fl
   adam_step(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nullptr, cur());
 }
 
-void adam_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr, float b1, float b2,
-                  float eps, float bc1, float bc2, float wd, bool decoupled, const uint8_t* nodecay) {
-  adam_step_nodecay(p, g, m, v, static_cast<bf16*>(shadow), n, lr, b1, b2, eps, bc1, bc2, wd, decoupled ? 1 : 0, nullptr,
-                    nodecay, cur());
-}
-void adam_dev_nodecay(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2,
-                      float eps, float wd, bool decoupled, const float* hyper, const uint8_t* nodecay) {
-  adam_step_nodecay(p, g, m, v, static_cast<bf16*>(shadow), n, 0.f, b1, b2, eps, 1.f, 1.f, wd, decoupled ? 1 : 0, hyper,
-                    nodecay, cur());
-}
-
 const void* loss_device() { return scratch(LOSS_OUT, 16); }
 
 void adam_hyper_step(float* hyper, float b1, float b2) { adam_scalars(hyper, b1, b2, cur()); }
 void adam_dev(float* p, const float* g, float* m, float* v, void* shadow, long n, float b1, float b2, float eps,
-              float wd, bool decoupled, const float* hyper) {
-  adam_step(p, g, m, v, static_cast<bf16*>(shadow), n, 0.f, b1, b2, eps, 1.f, 1.f, wd, decoupled ? 1 : 0, hyper, cur());
+              float wd, bool decoupled, const float* hyper, const uint8_t* nodecay) {
+  bf16* sh = static_cast<bf16*>(shadow);
+  if (nodecay)
+    adam_step_nodecay(p, g, m, v, sh, n, 0.f, b1, b2, eps, 1.f, 1.f, wd, decoupled ? 1 : 0, hyper, nodecay, cur());
+  else
+    adam_step(p, g, m, v, sh, n, 0.f, b1, b2, eps, 1.f, 1.f, wd, decoupled ? 1 : 0, hyper, cur());
 }
 
 void sgd(float* p, const float* g, float* vel, void* shadow, long n, float lr, float momentum) {

@@ -30,6 +30,7 @@ With both off a step launches exactly what it launched before they existed.
 from __future__ import annotations
 
 import contextlib
+import inspect
 import math
 from typing import List, Optional
 
@@ -137,6 +138,49 @@ class Optimizer:
     def _on_attach(self):
         pass
 
+    def _need_no_decay_flags(self):
+        if self.no_decay_norm_bias and self.no_decay is None:
+            raise ValueError("no_decay_norm_bias needs to know which parameters are biases, norm affines or "
+                             "layer scales: attach a model or an arena, or pass no_decay=[...]")
+
+    def fused(self) -> bool:
+        """The step is the fused launch over a GPU arena's flat buffers."""
+        return self.arena is not None and self._flat_p.is_cuda
+
+    def prepare_step(self) -> None:
+        """Host side of a step (graph-replay safe): host counters, and the device scalars when stale."""
+
+    def launch_step(self) -> None:
+        """Device side of a fused step: the launches, reading their scalars from device memory."""
+        raise NotImplementedError
+
+    def _step_cpu_arena(self, cpu) -> None:
+        """The native flat-buffer step over a CPU arena (``cpu``: ``ops.cpu``; float32 or float64)."""
+        raise NotImplementedError
+
+    def _step_param(self, i, p, g) -> None:
+        """Parameter ``i`` in torch, under ``no_grad``; ``g`` is already scaled by the clip coefficient."""
+        raise NotImplementedError
+
+    def update(self) -> None:
+        """One step: fused over a GPU arena, the native flat-buffer loops over a CPU arena (then the
+        shadow refresh), else parameter by parameter in torch with the EMA behind each."""
+        self.prepare_step()
+        if self.fused():
+            self.launch_step()
+        elif self.arena is not None:
+            from ..ops import cpu
+            self._step_cpu_arena(cpu)
+            self.arena.sync_shadow()
+        else:
+            coef = self._host_coef()  # over all parameters, before any of them is stepped
+            with torch.no_grad():
+                for i, (p, g) in enumerate(zip(self.params, self.grads)):
+                    self._step_param(i, p, g if coef is None else g * coef)
+                    self._ema_torch(i, p)
+
+    step = property(lambda self: self.update)
+
     # ------------------------------------------------------------ gradient clipping / weight EMA
     def _tail(self) -> bool:
         return self.max_grad_norm > 0.0 or self.ema_decay > 0.0
@@ -180,6 +224,11 @@ class Optimizer:
         coef = c if (c < 1.0 or c != c) else 1.0
         self.grad_norm_device.copy_(torch.tensor([sumsq, norm, coef, self.max_grad_norm], dtype=torch.float64))
         return coef
+
+    def _tail_args(self, coef) -> dict:
+        """What a flat-buffer step takes beyond the plain one: the clip coefficient (None: off) and the
+        arena's EMA buffer (None: off) with its decay."""
+        return dict(coef=coef, ema=self.ema[0] if self.ema else None, ema_decay=self.ema_decay)
 
     def _ema_torch(self, i, p):
         if self.ema is not None:
@@ -233,11 +282,6 @@ class Optimizer:
         for dst, src in zip(self.ema or [], d.get("ema", [])):
             dst.copy_(src)
 
-    def update(self) -> None:
-        raise NotImplementedError
-
-    step = property(lambda self: self.update)
-
     def clear_gradients(self) -> None:
         if self.arena is not None:
             self.arena.zero_grad()
@@ -287,6 +331,24 @@ class Optimizer:
         self._hyper_ev[k] = ev
         return self._hyper
 
+    def _upload_hyper(self, vals):
+        """Fused path: upload the step scalars only when stale (first step, re-attach, learning-rate
+        change, loaded state)."""
+        if self.fused() and (self._hyper_dirty or self._hyper is None):
+            self._device_hyper(vals)
+            self._hyper_dirty = False
+
+    def name(self) -> str:
+        return type(self).__name__
+
+    def get_config(self) -> OptimizerConfig:
+        """Type string (the lower-case name, a key of ``_KINDS``) and that class's constructor arguments."""
+        kind = self.name().lower()
+        return OptimizerConfig(kind, self.name(), {k: getattr(self, k) for k in _hyper_names(_KINDS[kind])})
+
+    def clone(self) -> "Optimizer":
+        return OptimizerFactory.create_from_config(self.get_config())
+
     def state_dict(self) -> dict:
         return {}
 
@@ -294,210 +356,75 @@ class Optimizer:
         pass
 
 
-class SGD(Optimizer):
-    def __init__(self, learning_rate: float = 0.01, momentum: float = 0.0, max_grad_norm: float = 0.0,
-                 ema_decay: float = 0.0):
+def _hyper_names(cls) -> List[str]:
+    """The hyper-parameters of an optimizer class: its constructor's arguments, each kept as an
+    attribute of the same name."""
+    return [k for k in inspect.signature(cls.__init__).parameters if k != "self"]
+
+
+def _zeros_like_params(opt) -> List[torch.Tensor]:
+    """One state buffer: flat over the arena, else one tensor per parameter."""
+    return [opt.arena.new_zeros()] if opt.arena is not None else [torch.zeros_like(p) for p in opt.params]
+
+
+def _copy_state(dst, src) -> None:
+    for d, s in zip(dst or [], src or []):
+        d.copy_(s)
+
+
+class _VelocityState(Optimizer):
+    """SGD's and LARS's state: ``velocity`` (none with momentum 0) and the device scalars ``{lr}``."""
+
+    def __init__(self, learning_rate, momentum, max_grad_norm, ema_decay):
         super().__init__(learning_rate, max_grad_norm, ema_decay)
         self.momentum = float(momentum)
         self.velocity = None
 
     def _on_attach(self):
-        if self.momentum > 0:
-            if self.arena is not None:
-                self.velocity = [self.arena.new_zeros()]
-            else:
-                self.velocity = [torch.zeros_like(p) for p in self.params]
+        self.velocity = _zeros_like_params(self) if self.momentum > 0 else None
+
+    def _vel(self, i=0):
+        return self.velocity[i] if self.momentum > 0 else None
 
     def prepare_step(self):
-        if self.arena is not None and self._flat_p.is_cuda and (self._hyper_dirty or self._hyper is None):
-            self._device_hyper([self.learning_rate])
-            self._hyper_dirty = False
-
-    def launch_step(self):
-        from ..ops import hip
-        vel = self.velocity[0] if self.momentum > 0 else None
-        if self._tail():
-            hip.sgd_step_tail(self._flat_p, self._flat_g, vel, self.arena.shadow, self.learning_rate, self.momentum,
-                              self._hyper, self._launch_norm(), self.ema[0] if self.ema else None, self.ema_decay)
-        else:
-            hip.sgd_step(self._flat_p, self._flat_g, vel, self.arena.shadow, self.learning_rate, self.momentum,
-                         self._hyper)
-        self.arena.mark_synced()
-
-    def fused(self) -> bool:
-        return self.arena is not None and self._flat_p.is_cuda
-
-    def update(self):
-        if self.arena is not None:
-            p, g = self._flat_p, self._flat_g
-            if p.is_cuda:
-                self.prepare_step()
-                self.launch_step()
-                return
-            from ..ops import cpu
-            vel = self.velocity[0] if self.momentum > 0 else None
-            if self._tail():
-                cpu.sgd_step_tail(p, g, vel, self.learning_rate, self.momentum, self._host_coef(),
-                                  self.ema[0] if self.ema else None, self.ema_decay)
-            else:
-                cpu.sgd_step(p, g, vel, self.learning_rate, self.momentum)
-            self.arena.sync_shadow()
-            return
-        coef = self._host_coef()  # over all parameters, before any of them is stepped
-        for i, (p, g) in enumerate(zip(self.params, self.grads)):
-            self._sgd_torch(p, g if coef is None else g * coef, self.velocity[i] if self.momentum > 0 else None)
-            with torch.no_grad():
-                self._ema_torch(i, p)
-
-    def _sgd_torch(self, p, g, v):
-        with torch.no_grad():
-            if v is not None:
-                v.mul_(self.momentum).sub_(self.learning_rate * g)
-                p.add_(v)
-            else:
-                p.sub_(self.learning_rate * g)
-
-    def name(self):
-        return "SGD"
-
-    def get_config(self):
-        return OptimizerConfig("sgd", "SGD", {"learning_rate": self.learning_rate, "momentum": self.momentum,
-                                              "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay})
-
-    def clone(self):
-        return SGD(self.learning_rate, self.momentum, self.max_grad_norm, self.ema_decay)
+        self._upload_hyper([self.learning_rate])
 
     def state_dict(self):
-        return {"velocity": [v.detach().cpu() for v in self.velocity] if self.velocity else [], **self._tail_state()}
+        return {"velocity": [v.detach().cpu() for v in self.velocity or []], **self._tail_state()}
 
     def load_state_dict(self, d):
         self._load_tail_state(d)
-        if d.get("velocity") and self.velocity:
-            for v, s in zip(self.velocity, d["velocity"]):
-                v.copy_(s)
+        _copy_state(self.velocity, d.get("velocity"))
 
 
-class Adam(Optimizer):
-    def __init__(self, learning_rate: float = 0.001, beta1: float = 0.9, beta2: float = 0.999,
-                 epsilon: float = 1e-8, weight_decay: float = 0.0, decouple_weight_decay: bool = False,
-                 no_decay_norm_bias: bool = False, max_grad_norm: float = 0.0, ema_decay: float = 0.0):
-        """``no_decay_norm_bias``: biases, norm affines and layer scales take the step without
-        weight decay. On the fused arena path a static device table of one byte per 64-element
-        block selects them inside the one launch; off (the default), the launch is unchanged.
-        ``max_grad_norm`` / ``ema_decay``: global-norm clipping and the weight EMA (module docstring);
-        with either on, the step is the norm reduction plus one instance of the step kernel that
-        reads the coefficient and maintains the EMA."""
+class _MomentState(Optimizer):
+    """Adam's and LAMB's state: the step count ``t``, the moments ``m`` and ``v``, and the device
+    scalars ``{lr, bc1, bc2, t}``."""
+
+    def __init__(self, learning_rate, beta1, beta2, epsilon, max_grad_norm, ema_decay):
         super().__init__(learning_rate, max_grad_norm, ema_decay)
-        self.no_decay_norm_bias = bool(no_decay_norm_bias)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
-        self.weight_decay = float(weight_decay)
-        self.decouple_weight_decay = bool(decouple_weight_decay)
         self.t = 0
         self.m = self.v = None
 
     def _on_attach(self):
-        if self.arena is not None:
-            self.m = [self.arena.new_zeros()]
-            self.v = [self.arena.new_zeros()]
-        else:
-            self.m = [torch.zeros_like(p) for p in self.params]
-            self.v = [torch.zeros_like(p) for p in self.params]
+        self.m, self.v = _zeros_like_params(self), _zeros_like_params(self)
         self.t = 0
-        self._nodecay_blocks = None
-        if self.no_decay_norm_bias:
-            if self.no_decay is None:
-                raise ValueError("no_decay_norm_bias needs to know which parameters are biases, norm affines or "
-                                 "layer scales: attach a model or an arena, or pass no_decay=[...]")
-            if self.arena is not None:
-                self._nodecay_blocks = self.arena.no_decay_blocks()
-
-    def fused(self) -> bool:
-        return self.arena is not None and self._flat_p.is_cuda
 
     def prepare_step(self):
-        """Host side of a step (graph-replay safe): advance the host step counter; upload the
-        device scalars only when stale (first step, learning-rate change, loaded state) — the
-        device counter then equals t - 1 and ``launch_step`` advances it on the device."""
+        """Advance the host step counter and take the bias corrections; upload the device scalars only
+        when stale — the device counter then equals t - 1 and ``launch_step`` advances it on the
+        device (``adam_scalars`` / ``lamb_scalars``)."""
         self.t += 1
         self._bc = (1.0 - self.beta1 ** self.t, 1.0 - self.beta2 ** self.t)
-        if self.fused() and (self._hyper_dirty or self._hyper is None):
-            self._device_hyper([self.learning_rate, 0.0, 0.0, float(self.t - 1)])
-            self._hyper_dirty = False
+        self._upload_hyper([self.learning_rate, 0.0, 0.0, float(self.t - 1)])
 
-    def launch_step(self):
-        """Device side: the scalar update (t, bias corrections) and ONE kernel over the flat
-        buffer, both reading their scalars from device memory."""
-        from ..ops import hip
-        from ..ops._ext import kernels, stream_ptr
-        kernels().adam_scalars(self._hyper.data_ptr(), float(self.beta1), float(self.beta2),
-                               stream_ptr(self._flat_p.device))
-        bc1, bc2 = self._bc
-        args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate, self.beta1,
-                self.beta2, self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay, self._hyper)
-        if self._tail():
-            hip.adam_step_tail(*args, nodecay=self._nodecay_blocks, coef=self._launch_norm(),
-                               ema=self.ema[0] if self.ema else None, ema_decay=self.ema_decay)
-        else:
-            hip.adam_step(*args, nodecay=self._nodecay_blocks)
-        self.arena.mark_synced()
-
-    def update(self):
-        if self.fused():
-            self.prepare_step()
-            self.launch_step()
-            return
-        self.t += 1
-        bc1 = 1.0 - self.beta1 ** self.t
-        bc2 = 1.0 - self.beta2 ** self.t
-        if self.arena is not None and not self._flat_p.is_cuda:
-            from ..ops import cpu   # native flat-buffer step (CPU arena, float32 or float64)
-            args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1, self.beta2,
-                    self.epsilon, bc1, bc2, self.weight_decay, self.decouple_weight_decay)
-            if self._tail():
-                cpu.adam_step_tail(*args, self._nodecay_blocks, self._host_coef(), self.ema[0] if self.ema else None,
-                                   self.ema_decay)
-            elif self._nodecay_blocks is not None:
-                cpu.adam_step_nodecay(*args, self._nodecay_blocks)
-            else:
-                cpu.adam_step(*args)
-            self.arena.sync_shadow()
-            return
-        pairs = [(self._flat_p, self._flat_g)] if self.arena is not None else list(zip(self.params, self.grads))
-        coef = self._host_coef()  # over all parameters, before any of them is stepped
-        with torch.no_grad():
-            for i, (p, g) in enumerate(pairs):
-                m, v = self.m[i], self.v[i]
-                if coef is not None:
-                    g = g * coef
-                m.mul_(self.beta1).add_((1 - self.beta1) * g)
-                v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
-                upd = self.learning_rate * (m / bc1) / (torch.sqrt(v / bc2) + self.epsilon)
-                wd = 0.0 if (self.no_decay_norm_bias and self.arena is None and self.no_decay[i]) else self.weight_decay
-                if wd > 0:
-                    if self.decouple_weight_decay:
-                        p.sub_(wd * self.learning_rate * p)
-                    else:
-                        upd = upd + wd * self.learning_rate * p
-                p.sub_(upd)
-                self._ema_torch(i, p)
-        if self.arena is not None:
-            self.arena.sync_shadow()
-
-    def name(self):
-        return "AdamW" if self.decouple_weight_decay else "Adam"
-
-    def get_config(self):
-        t = "adamw" if self.decouple_weight_decay else "adam"
-        return OptimizerConfig(t, self.name(), dict(learning_rate=self.learning_rate, beta1=self.beta1,
-                                                    beta2=self.beta2, epsilon=self.epsilon,
-                                                    weight_decay=self.weight_decay,
-                                                    decouple_weight_decay=self.decouple_weight_decay,
-                                                    no_decay_norm_bias=self.no_decay_norm_bias,
-                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
-
-    def clone(self):
-        return Adam(self.learning_rate, self.beta1, self.beta2, self.epsilon, self.weight_decay,
-                    self.decouple_weight_decay, self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
+    def _moments_torch(self, i, g):
+        """Parameter ``i`` in torch: m, v <- g; returns ``m_hat`` and ``sqrt(v_hat) + eps``."""
+        m, v = self.m[i], self.v[i]
+        m.mul_(self.beta1).add_((1 - self.beta1) * g)
+        v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
+        return m / self._bc[0], torch.sqrt(v / self._bc[1]) + self.epsilon
 
     def state_dict(self):
         return {"t": self.t, "m": [x.detach().cpu() for x in self.m or []], "v": [x.detach().cpu() for x in self.v or []],
@@ -507,10 +434,101 @@ class Adam(Optimizer):
         self._load_tail_state(d)
         self.t = int(d.get("t", 0))
         self._hyper_dirty = True
-        for dst, src in zip(self.m or [], d.get("m", [])):
-            dst.copy_(src)
-        for dst, src in zip(self.v or [], d.get("v", [])):
-            dst.copy_(src)
+        _copy_state(self.m, d.get("m"))
+        _copy_state(self.v, d.get("v"))
+
+
+class SGD(_VelocityState):
+    def __init__(self, learning_rate: float = 0.01, momentum: float = 0.0, max_grad_norm: float = 0.0,
+                 ema_decay: float = 0.0):
+        super().__init__(learning_rate, momentum, max_grad_norm, ema_decay)
+
+    def launch_step(self):
+        from ..ops import hip
+        args = (self._flat_p, self._flat_g, self._vel(), self.arena.shadow, self.learning_rate, self.momentum,
+                self._hyper)
+        if self._tail():
+            hip.sgd_step_tail(*args, **self._tail_args(self._launch_norm()))
+        else:
+            hip.sgd_step(*args)
+        self.arena.mark_synced()
+
+    def _step_cpu_arena(self, cpu):
+        args = (self._flat_p, self._flat_g, self._vel(), self.learning_rate, self.momentum)
+        if self._tail():
+            cpu.sgd_step_tail(*args, **self._tail_args(self._host_coef()))
+        else:
+            cpu.sgd_step(*args)
+
+    def _step_param(self, i, p, g):
+        v = self._vel(i)
+        if v is not None:
+            v.mul_(self.momentum).sub_(self.learning_rate * g)
+            p.add_(v)
+        else:
+            p.sub_(self.learning_rate * g)
+
+
+class Adam(_MomentState):
+    def __init__(self, learning_rate: float = 0.001, beta1: float = 0.9, beta2: float = 0.999,
+                 epsilon: float = 1e-8, weight_decay: float = 0.0, decouple_weight_decay: bool = False,
+                 no_decay_norm_bias: bool = False, max_grad_norm: float = 0.0, ema_decay: float = 0.0):
+        """``no_decay_norm_bias``: biases, norm affines and layer scales take the step without
+        weight decay. On the fused arena path a static device table of one byte per 64-element
+        block selects them inside the one launch; off (the default), the launch is unchanged.
+        ``max_grad_norm`` / ``ema_decay``: global-norm clipping and the weight EMA (module docstring);
+        with either on, the step is the norm reduction plus one instance of the step kernel that
+        reads the coefficient and maintains the EMA."""
+        super().__init__(learning_rate, beta1, beta2, epsilon, max_grad_norm, ema_decay)
+        self.no_decay_norm_bias = bool(no_decay_norm_bias)
+        self.weight_decay = float(weight_decay)
+        self.decouple_weight_decay = bool(decouple_weight_decay)
+
+    def _on_attach(self):
+        super()._on_attach()
+        self._need_no_decay_flags()
+        on = self.no_decay_norm_bias and self.arena is not None
+        self._nodecay_blocks = self.arena.no_decay_blocks() if on else None
+
+    def _scalars(self):
+        return (self.learning_rate, self.beta1, self.beta2, self.epsilon, *self._bc, self.weight_decay,
+                self.decouple_weight_decay)
+
+    def launch_step(self):
+        """The scalar update (t, bias corrections) and ONE kernel over the flat buffer."""
+        from ..ops import hip
+        from ..ops._ext import kernels, stream_ptr
+        kernels().adam_scalars(self._hyper.data_ptr(), float(self.beta1), float(self.beta2),
+                               stream_ptr(self._flat_p.device))
+        args = (self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, *self._scalars(), self._hyper)
+        if self._tail():
+            hip.adam_step_tail(*args, nodecay=self._nodecay_blocks, **self._tail_args(self._launch_norm()))
+        else:
+            hip.adam_step(*args, nodecay=self._nodecay_blocks)
+        self.arena.mark_synced()
+
+    def _step_cpu_arena(self, cpu):
+        args = (self._flat_p, self._flat_g, self.m[0], self.v[0], *self._scalars())
+        if self._tail():
+            cpu.adam_step_tail(*args, nodecay=self._nodecay_blocks, **self._tail_args(self._host_coef()))
+        elif self._nodecay_blocks is not None:
+            cpu.adam_step_nodecay(*args, self._nodecay_blocks)
+        else:
+            cpu.adam_step(*args)
+
+    def _step_param(self, i, p, g):
+        m_hat, denom = self._moments_torch(i, g)
+        upd = self.learning_rate * m_hat / denom
+        wd = 0.0 if (self.no_decay_norm_bias and self.no_decay[i]) else self.weight_decay
+        if wd > 0:
+            if self.decouple_weight_decay:
+                p.sub_(wd * self.learning_rate * p)
+            else:
+                upd = upd + wd * self.learning_rate * p
+        p.sub_(upd)
+
+    def name(self):
+        return "AdamW" if self.decouple_weight_decay else "Adam"
 
 
 class AdamW(Adam):
@@ -536,11 +554,10 @@ class _Layerwise(Optimizer):
         self.no_decay_norm_bias = bool(no_decay_norm_bias)
         self._tables = self._trust = self._part = None
 
-    def _attach_layerwise(self):
+    def _on_attach(self):
+        super()._on_attach()  # (the moment or velocity state)
         self._tables = self._trust = self._part = None
-        if self.no_decay_norm_bias and self.no_decay is None:
-            raise ValueError("no_decay_norm_bias needs to know which parameters are biases, norm affines or "
-                             "layer scales: attach a model or an arena, or pass no_decay=[...]")
+        self._need_no_decay_flags()
         if self.arena is not None:
             self._tables = self.arena.segment_tables(self.no_decay_norm_bias)
             if self._flat_p.is_cuda:
@@ -553,9 +570,6 @@ class _Layerwise(Optimizer):
 
     def _excluded(self, i) -> bool:
         return self.no_decay_norm_bias and self.no_decay[i]
-
-    def fused(self) -> bool:
-        return self.arena is not None and self._flat_p.is_cuda
 
     def last_trust_ratios(self) -> List[float]:
         """The trust ratio of every parameter in the last step (1.0 before the first), read on the
@@ -579,103 +593,50 @@ class _Layerwise(Optimizer):
         return math.sqrt(float((t.detach().double() ** 2).sum()))
 
 
-class LAMB(_Layerwise):
+
+
+
+class LAMB(_Layerwise, _MomentState):
     """LAMB (You et al. 2019): Adam's moments, the update ``r = (m / bc1) / (sqrt(v / bc2) + eps) +
     wd p`` scaled per parameter by ``trust = ||p|| / ||r||``: ``p -= lr trust r``. State as Adam's
-    (``t``, ``m``, ``v``)."""
+    (``t``, ``m``, ``v``; the device scalars advance by ``lamb_scalars``: the bias corrections in double)."""
 
     def __init__(self, learning_rate: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-6,
                  weight_decay: float = 0.01, no_decay_norm_bias: bool = False, max_grad_norm: float = 0.0,
                  ema_decay: float = 0.0):
-        super().__init__(learning_rate, max_grad_norm, ema_decay)
+        super().__init__(learning_rate, beta1, beta2, epsilon, max_grad_norm, ema_decay)
         self._init_layerwise(weight_decay, no_decay_norm_bias)
-        self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
-        self.t = 0
-        self.m = self.v = None
 
-    def _on_attach(self):
-        if self.arena is not None:
-            self.m = [self.arena.new_zeros()]
-            self.v = [self.arena.new_zeros()]
-        else:
-            self.m = [torch.zeros_like(p) for p in self.params]
-            self.v = [torch.zeros_like(p) for p in self.params]
-        self.t = 0
-        self._attach_layerwise()
-
-    def prepare_step(self):
-        """As ``Adam.prepare_step``: the host counter advances, the device scalars are uploaded only
-        when stale and advance on the device (``lamb_scalars``: the bias corrections in double)."""
-        self.t += 1
-        self._bc = (1.0 - self.beta1 ** self.t, 1.0 - self.beta2 ** self.t)
-        if self.fused() and (self._hyper_dirty or self._hyper is None):
-            self._device_hyper([self.learning_rate, 0.0, 0.0, float(self.t - 1)])
-            self._hyper_dirty = False
+    def _scalars(self):
+        return (self.learning_rate, self.beta1, self.beta2, self.epsilon, *self._bc, self.weight_decay)
 
     def launch_step(self):
         from ..ops import hip
         from ..ops._ext import kernels, stream_ptr
         kernels().lamb_scalars(self._hyper.data_ptr(), float(self.beta1), float(self.beta2),
                                stream_ptr(self._flat_p.device))
-        bc1, bc2 = self._bc
-        hip.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, self.learning_rate,
-                      self.beta1, self.beta2, self.epsilon, bc1, bc2, self.weight_decay, self._tables, self._trust,
-                      self._part, hyper=self._hyper, coef=self._launch_norm(), ema=self.ema[0] if self.ema else None,
-                      ema_decay=self.ema_decay)
+        hip.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.arena.shadow, *self._scalars(),
+                      self._tables, self._trust, self._part, hyper=self._hyper,
+                      **self._tail_args(self._launch_norm()))
         self.arena.mark_synced()
 
-    def update(self):
-        if self.fused():
-            self.prepare_step()
-            self.launch_step()
-            return
-        self.t += 1
-        bc1 = 1.0 - self.beta1 ** self.t
-        bc2 = 1.0 - self.beta2 ** self.t
-        if self.arena is not None:
-            from ..ops import cpu   # native flat-buffer step (CPU arena, float32 or float64)
-            cpu.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], self.learning_rate, self.beta1, self.beta2,
-                          self.epsilon, bc1, bc2, self.weight_decay, self._tables, self._trust, self._host_coef(),
-                          self.ema[0] if self.ema else None, self.ema_decay)
-            self.arena.sync_shadow()
-            return
-        coef = self._host_coef()  # over all parameters, before any of them is stepped
-        with torch.no_grad():
-            for i, (p, g) in enumerate(zip(self.params, self.grads)):
-                m, v = self.m[i], self.v[i]
-                if coef is not None:
-                    g = g * coef
-                m.mul_(self.beta1).add_((1 - self.beta1) * g)
-                v.mul_(self.beta2).add_((1 - self.beta2) * g * g)
-                r = (m / bc1) / (torch.sqrt(v / bc2) + self.epsilon)
-                trust = 1.0
-                if not self._excluded(i):
-                    r = r + self.weight_decay * p
-                    pn, rn = self._norm(p), self._norm(r)
-                    trust = 1.0 if (pn == 0.0 or rn == 0.0) else pn / rn
-                self._trust[i] = trust
-                p.sub_(self.learning_rate * trust * r)
-                self._ema_torch(i, p)
+    def _step_cpu_arena(self, cpu):
+        cpu.lamb_step(self._flat_p, self._flat_g, self.m[0], self.v[0], *self._scalars(), self._tables, self._trust,
+                      **self._tail_args(self._host_coef()))
 
-    def name(self):
-        return "LAMB"
-
-    def get_config(self):
-        return OptimizerConfig("lamb", "LAMB", dict(learning_rate=self.learning_rate, beta1=self.beta1,
-                                                    beta2=self.beta2, epsilon=self.epsilon,
-                                                    weight_decay=self.weight_decay,
-                                                    no_decay_norm_bias=self.no_decay_norm_bias,
-                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
-
-    def clone(self):
-        return LAMB(self.learning_rate, self.beta1, self.beta2, self.epsilon, self.weight_decay,
-                    self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
-
-    state_dict = Adam.state_dict
-    load_state_dict = Adam.load_state_dict
+    def _step_param(self, i, p, g):
+        m_hat, denom = self._moments_torch(i, g)
+        r = m_hat / denom
+        trust = 1.0
+        if not self._excluded(i):
+            r = r + self.weight_decay * p
+            pn, rn = self._norm(p), self._norm(r)
+            trust = 1.0 if (pn == 0.0 or rn == 0.0) else pn / rn
+        self._trust[i] = trust
+        p.sub_(self.learning_rate * trust * r)
 
 
-class LARS(_Layerwise):
+class LARS(_Layerwise, _VelocityState):
     """LARS (You et al. 2017): momentum SGD with L2 weight decay, the step of every parameter scaled
     by ``trust = tc ||p|| / (||g|| + wd ||p|| + eps)``: ``v = mom v - lr trust (g + wd p)``, ``p += v``
     (the velocity convention of :class:`SGD`; momentum 0: no velocity buffer). State as SGD's."""
@@ -683,106 +644,56 @@ class LARS(_Layerwise):
     def __init__(self, learning_rate: float = 0.1, momentum: float = 0.9, weight_decay: float = 5e-4,
                  trust_coefficient: float = 1e-3, epsilon: float = 1e-8, no_decay_norm_bias: bool = False,
                  max_grad_norm: float = 0.0, ema_decay: float = 0.0):
-        super().__init__(learning_rate, max_grad_norm, ema_decay)
+        super().__init__(learning_rate, momentum, max_grad_norm, ema_decay)
         self._init_layerwise(weight_decay, no_decay_norm_bias)
-        self.momentum = float(momentum)
         self.trust_coefficient, self.epsilon = float(trust_coefficient), float(epsilon)
-        self.velocity = None
 
-    def _on_attach(self):
-        self.velocity = None
-        if self.momentum > 0:
-            if self.arena is not None:
-                self.velocity = [self.arena.new_zeros()]
-            else:
-                self.velocity = [torch.zeros_like(p) for p in self.params]
-        self._attach_layerwise()
-
-    def prepare_step(self):
-        if self.fused() and (self._hyper_dirty or self._hyper is None):
-            self._device_hyper([self.learning_rate])
-            self._hyper_dirty = False
+    def _scalars(self):
+        return (self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon)
 
     def launch_step(self):
         from ..ops import hip
-        hip.lars_step(self._flat_p, self._flat_g, self.velocity[0] if self.momentum > 0 else None, self.arena.shadow,
-                      self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
-                      self._tables, self._trust, self._part, hyper=self._hyper, coef=self._launch_norm(),
-                      ema=self.ema[0] if self.ema else None, ema_decay=self.ema_decay)
+        hip.lars_step(self._flat_p, self._flat_g, self._vel(), self.arena.shadow, *self._scalars(), self._tables,
+                      self._trust, self._part, hyper=self._hyper, **self._tail_args(self._launch_norm()))
         self.arena.mark_synced()
 
-    def update(self):
-        if self.fused():
-            self.prepare_step()
-            self.launch_step()
-            return
-        if self.arena is not None:
-            from ..ops import cpu
-            cpu.lars_step(self._flat_p, self._flat_g, self.velocity[0] if self.momentum > 0 else None,
-                          self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
-                          self._tables, self._trust, self._host_coef(), self.ema[0] if self.ema else None,
-                          self.ema_decay)
-            self.arena.sync_shadow()
-            return
-        coef = self._host_coef()  # over all parameters, before any of them is stepped
-        with torch.no_grad():
-            for i, (p, g) in enumerate(zip(self.params, self.grads)):
-                if coef is not None:
-                    g = g * coef
-                trust, wd = 1.0, 0.0
-                if not self._excluded(i):
-                    wd = self.weight_decay
-                    pn, gn = self._norm(p), self._norm(g)
-                    if not (pn == 0.0 or gn == 0.0):
-                        trust = self.trust_coefficient * pn / (gn + wd * pn + self.epsilon)
-                self._trust[i] = trust
-                u = g + wd * p
-                if self.momentum > 0:
-                    self.velocity[i].mul_(self.momentum).sub_(self.learning_rate * trust * u)
-                    p.add_(self.velocity[i])
-                else:
-                    p.sub_(self.learning_rate * trust * u)
-                self._ema_torch(i, p)
+    def _step_cpu_arena(self, cpu):
+        cpu.lars_step(self._flat_p, self._flat_g, self._vel(), *self._scalars(), self._tables, self._trust,
+                      **self._tail_args(self._host_coef()))
 
-    def name(self):
-        return "LARS"
+    def _step_param(self, i, p, g):
+        trust, wd = 1.0, 0.0
+        if not self._excluded(i):
+            wd = self.weight_decay
+            pn, gn = self._norm(p), self._norm(g)
+            if not (pn == 0.0 or gn == 0.0):
+                trust = self.trust_coefficient * pn / (gn + wd * pn + self.epsilon)
+        self._trust[i] = trust
+        u = g + wd * p
+        v = self._vel(i)
+        if v is not None:
+            v.mul_(self.momentum).sub_(self.learning_rate * trust * u)
+            p.add_(v)
+        else:
+            p.sub_(self.learning_rate * trust * u)
 
-    def get_config(self):
-        return OptimizerConfig("lars", "LARS", dict(learning_rate=self.learning_rate, momentum=self.momentum,
-                                                    weight_decay=self.weight_decay,
-                                                    trust_coefficient=self.trust_coefficient, epsilon=self.epsilon,
-                                                    no_decay_norm_bias=self.no_decay_norm_bias,
-                                                    max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay))
 
-    def clone(self):
-        return LARS(self.learning_rate, self.momentum, self.weight_decay, self.trust_coefficient, self.epsilon,
-                    self.no_decay_norm_bias, self.max_grad_norm, self.ema_decay)
-
-    state_dict = SGD.state_dict
-    load_state_dict = SGD.load_state_dict
+# config type string -> the class whose constructor arguments are the config's parameters
+_KINDS = {"sgd": SGD, "adam": Adam, "adamw": Adam, "lamb": LAMB, "lars": LARS}
 
 
 class OptimizerFactory:
     @staticmethod
     def create_from_config(config) -> Optimizer:
+        """Parameters the config leaves out take the constructor's defaults, keys the constructor does
+        not know are ignored. ``adamw`` is :class:`Adam` with ``decouple_weight_decay`` on by default."""
         if isinstance(config, dict) and not isinstance(config, OptimizerConfig):
             config = OptimizerConfig.from_json(config)
         t = config["type"]
         p = config["parameters"]
-        if t == "sgd":
-            return SGD(p.get("learning_rate", 0.01), p.get("momentum", 0.0), p.get("max_grad_norm", 0.0),
-                       p.get("ema_decay", 0.0))
-        if t in ("adam", "adamw"):
-            return Adam(p.get("learning_rate", 0.001), p.get("beta1", 0.9), p.get("beta2", 0.999),
-                        p.get("epsilon", 1e-8), p.get("weight_decay", 0.0),
-                        p.get("decouple_weight_decay", t == "adamw"), p.get("no_decay_norm_bias", False),
-                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
-        if t == "lamb":
-            return LAMB(p.get("learning_rate", 1e-3), p.get("beta1", 0.9), p.get("beta2", 0.999),
-                        p.get("epsilon", 1e-6), p.get("weight_decay", 0.01), p.get("no_decay_norm_bias", False),
-                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
-        if t == "lars":
-            return LARS(p.get("learning_rate", 0.1), p.get("momentum", 0.9), p.get("weight_decay", 5e-4),
-                        p.get("trust_coefficient", 1e-3), p.get("epsilon", 1e-8), p.get("no_decay_norm_bias", False),
-                        p.get("max_grad_norm", 0.0), p.get("ema_decay", 0.0))
-        raise ValueError(f"Unknown optimizer type: {t}")
+        if t not in _KINDS:
+            raise ValueError(f"Unknown optimizer type: {t}")
+        given = {k: p[k] for k in _hyper_names(_KINDS[t]) if k in p}
+        if t == "adamw":
+            given.setdefault("decouple_weight_decay", True)
+        return _KINDS[t](**given)

@@ -170,6 +170,42 @@ def test_optimizer_factory_and_config():
     assert o.get_learning_rate() == 0.05
 
 
+_TAIL_OFF = {"max_grad_norm": 0.0, "ema_decay": 0.0}
+_ADAM_DEFAULTS = {"learning_rate": 0.001, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8, "weight_decay": 0.0,
+                  "decouple_weight_decay": False, "no_decay_norm_bias": False, **_TAIL_OFF}
+_FACTORY_DEFAULTS = {
+    "sgd": ("SGD", {"learning_rate": 0.01, "momentum": 0.0, **_TAIL_OFF}),
+    "adam": ("Adam", _ADAM_DEFAULTS),
+    # (the factory's adamw is Adam with the decay decoupled and still 0, not AdamW()'s 0.01)
+    "adamw": ("AdamW", {**_ADAM_DEFAULTS, "decouple_weight_decay": True}),
+    "lamb": ("LAMB", {"learning_rate": 0.001, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-6, "weight_decay": 0.01,
+                      "no_decay_norm_bias": False, **_TAIL_OFF}),
+    "lars": ("LARS", {"learning_rate": 0.1, "momentum": 0.9, "weight_decay": 0.0005, "trust_coefficient": 0.001,
+                      "epsilon": 1e-8, "no_decay_norm_bias": False, **_TAIL_OFF}),
+}
+
+
+def test_optimizer_config_defaults_and_round_trips():
+    """The defaults a config may leave out, per type, and get_config through the factory and clone()."""
+    from dcnn_amd.nn import LAMB, LARS
+    for kind, (name, params) in _FACTORY_DEFAULTS.items():
+        cfg = OptimizerFactory.create_from_config({"type": kind, "parameters": {}}).get_config()
+        assert dict(cfg) == {"type": kind, "name": name, "parameters": params}, kind
+    assert AdamW().get_config()["parameters"] == {**_ADAM_DEFAULTS, "decouple_weight_decay": True, "weight_decay": 0.01}
+    for o in (SGD(), Adam(), AdamW(), LAMB(), LARS(), SGD(0.2, 0.5, 1.5, 0.9),
+              Adam(0.003, 0.8, 0.99, 1e-7, 0.02, True, True, 2.0, 0.5), AdamW(0.004, weight_decay=0.03),
+              LAMB(0.002, 0.8, 0.99, 1e-5, 0.1, True, 1.0, 0.99),
+              LARS(0.3, 0.0, 1e-3, 2e-3, 1e-6, True, 0.5, 0.9)):
+        cfg = o.get_config()
+        assert OptimizerFactory.create_from_config(cfg).get_config() == cfg
+        assert o.clone().get_config() == cfg and o.clone() is not o
+    # a key the type does not know is ignored; "adam" honours decouple_weight_decay
+    o = OptimizerFactory.create_from_config({"type": "adam", "parameters": {"decouple_weight_decay": True, "nope": 1}})
+    assert o.name() == "AdamW" and o.get_config()["type"] == "adamw"
+    with pytest.raises(ValueError, match="Unknown optimizer type: rmsprop"):
+        OptimizerFactory.create_from_config({"type": "rmsprop", "parameters": {}})
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("opt_name", ["sgd_momentum", "adam", "adamw"])
 def test_optimizer_gpu_matches_cpu(opt_name):
